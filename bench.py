@@ -39,6 +39,11 @@ The other configurations (single GPU, one JSON line each; evidence for the numbe
     python bench.py --config agc        # automatic gain control, same shapes
     python bench.py --config biquad     # stand-alone low_pass: mode 1 (time-parallel) and mode 0 (reference order)
     python bench.py --config stream     # the headline workload STREAMED in blocks of --block input frames (rh_rlm_stream_block_v on resident rows)
+
+`--steps K` is the number of timed steps (of the head kernel, in the side configurations; the default line's side legs keep their own
+counts) and `ms_per_step` the wall time of one of them.  `--dump-outputs DIR` writes, after the timed steps, what the last one
+computed -- the arrays a caller of the timed path receives -- as DIR/<name>.npy: the mixed block `mix.npy` for the default line.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -59,6 +64,32 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
+DUMP_BYTES = 64_000_000  # --dump-outputs: at most this many bytes of samples in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: the arrays the timed path handed its caller in its last step, one DIR/<name>.npy each, f32 as computed.
+    Every array gets an equal share of DUMP_BYTES; one larger than its share is written as a fixed sample of its flattened
+    elements, the indices np.unique(default_rng(0).integers(0, numel, share)) -- the same for every run of the same arguments,
+    so two builds compare element for element.  Returns what was written (it goes into the JSON line as `outputs`)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        cap = (share - 1024) // flat.element_size()  # (room for the .npy header)
+        if flat.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), cap))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not f32 / f64")
+        np.save(os.path.join(d, name + ".npy"), a)
+        info[name] = {"shape": list(t.shape), "dtype": str(a.dtype), "elements_written": int(a.size), "sampled": bool(a.size != t.numel())}
+    return {"dir": os.path.abspath(d), "arrays": info}
 
 
 def make_sources(S, N, first, total, ch=2):
@@ -108,13 +139,9 @@ def pmc_traffic(argv, kernel_like, per_call=False):
         d = tempfile.mkdtemp(prefix="rh_pmc_", dir="/tmp")
         try:
             cmd = [exe, "--pmc", counter, "-d", d, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
-            for attempt in (0, 1):  # (a profiler pass that dies on its way up is tried once more: seen once in a long session, never twice)
-                r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-                dbs = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
-                if r.returncode == 0 and dbs:
-                    break
-                shutil.rmtree(d, ignore_errors=True)
-                os.makedirs(d, exist_ok=True)
+            # one pass: a profiler pass that fails is reported in the line, not run again on the GPU
+            r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+            dbs = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
             if r.returncode != 0 or not dbs:
                 return None, f"rocprofv3 --pmc {counter} failed (rc {r.returncode}): " + r.stderr.decode(errors="replace")[-300:]
             con = sqlite3.connect(dbs[0])
@@ -425,6 +452,7 @@ def headline(args, argv):
         if rank == 0:
             emit({"child": True, "kernel_ms": kernel_avg_ms, "calls": args.warmup + args.steps})
         return
+    dumped = dump_outputs(args.dump_outputs, {"mix": mixed_last}) if args.dump_outputs and rank == 0 else None
 
     # ---- untimed diagnostics of the N > 1 path: the collective alone, the reduced block against the ranks' partials, the ranks seen --
     multi = None
@@ -849,6 +877,8 @@ def headline(args, argv):
         res["cpu_baseline"] = base
     if parity is not None:
         res["parity"] = parity
+    if dumped is not None:
+        res["outputs"] = dumped
     emit(res)
 
 
@@ -891,6 +921,7 @@ def side(args, argv, lite=False):
     checks = None  # () -> (parity dict, cpu_baseline dict), run once after the timing
     like = "%"
     per_call = False
+    dumps = {}  # --dump-outputs: name -> () -> the output tensor the caller of each timed entry receives
 
     if cfg == "3":
         from oracle import rodio_oracle as O
@@ -904,6 +935,7 @@ def side(args, argv, lite=False):
         gd = rh.spatial_gains_batch(em, [-1, 0, 0], [1, 0, 0])
         alg = 4 * S * n + 4 * S * (n + d)
         kernels.append(("reverb_spatial", lambda: rh.reverb_spatial_batch(x, 48000, ns, 0.3, None, None, None, out=out, gains_dev=gd), alg, S * n))
+        dumps["reverb_spatial"] = lambda: out
         workload = f"reverb({ns} ns = {d} samples, 0.3) -> Spatial on {S} sources x {n} interleaved stereo samples @ 48 kHz, default_rng(5678+s) U(-1,1)*0.25 (BASELINE config 3), one fused launch"
         metric = "Msamples/s through reverb+spatial"
         like = "%reverb_spatial%"
@@ -944,6 +976,7 @@ def side(args, argv, lite=False):
         mf = C.c_uint64(0)
         kernels.append(("wav_decode_and_channels_6_to_2_one_launch", lambda: _lib.check(lib.rh_wav_decode_channels(C.c_void_p(out2f.data_ptr()), C.c_void_p(d_raw.data_ptr()), frames6 * 6, 6, 16, 0, 2, C.byref(mf), stream),
                                                                                      "rh_wav_decode_channels"), 12 * frames6 + 8 * frames6, frames6 * 6))
+        dumps.update(wav_decode_i16_to_f32=lambda: f32[:n], channels_6_to_2=lambda: out2, wav_decode_and_channels_6_to_2_one_launch=lambda: out2f[: mf.value])
         workload = (f"assets/music.wav data chunk ({info['samples']} PCM16 samples, RIFF probed by rh_wav_probe_host) tiled x{tile} = {n} samples: i16 -> f32 on the device "
                     f"(rh_wav_decode), then the f32 stream re-framed as {frames6} frames x 6 ch -> ChannelCountConverter(6 -> 2) (BASELINE config 5)")
         metric = "Msamples/s through i16->f32 DataConverter"
@@ -972,9 +1005,11 @@ def side(args, argv, lite=False):
         alg = 8 * S * 2 * n
         if cfg == "limit":
             kernels.append(("limit", lambda: rh.limit_batch(x, 2, 48000, out=out), alg, S * 2 * n))
+            dumps["limit"] = lambda: out
             like, chain, tol = "%k_limit_scan%", (lambda src: src.limit()), 1e-5
         elif cfg == "agc":
             kernels.append(("agc", lambda: rh.agc_batch(x, 48000, out=out), alg, S * 2 * n))
+            dumps["agc"] = lambda: out
             like, chain, tol, per_call = "%k_agc%", (lambda src: src.automatic_gain_control()), 1e-5, True
         else:
             co = rh.biquad_coeffs("low_pass", 200, 0.5, 48000)
@@ -982,6 +1017,7 @@ def side(args, argv, lite=False):
             out0 = torch.empty_like(x)  # (outputs allocated once: a 512 MiB torch.empty_like per step costs the allocator more than the kernel takes)
             kernels.append(("biquad_time_parallel", lambda: outs_b.__setitem__("o", rh.biquad_batch(x, co, mode=1, out=out)), alg, S * 2 * n))
             kernels.append(("biquad_reference_order", lambda: rh.biquad_batch(x, co, mode=0, out=out0), alg, S * 2 * n))
+            dumps.update(biquad_time_parallel=lambda: outs_b["o"], biquad_reference_order=lambda: out0)
             like, chain, tol = "%k_biquad_scan%", (lambda src: src.low_pass(200)), 1e-5
         workload = f"{cfg}: {S} stereo streams x {n} frames @ 48 kHz, default settings, default_rng(4321+s) U(-1,1)*0.9, 4 B in + 4 B out per sample"
         metric = f"Msamples/s through {cfg}"
@@ -1050,6 +1086,7 @@ def side(args, argv, lite=False):
 
         alg = 4 * S * N * 2 + 4 * M * 2
         kernels.append((f"stream_block_v x {nblocks}", one_stream, alg, S * N * 2))
+        dumps["mix"] = lambda: out[: emitted[-1] * 2]
         workload = (f"block streaming of the headline workload: {S} resident f32 stereo sources x {N} frames in {nblocks} blocks of {B} input frames, 44.1->48 kHz + low_pass({args.freq}) + ordered "
                     f"Mixer sum per block through rh_rlm_stream_block_v (sources that run together: the summed state, mix first); one step = one whole stream")
         metric = "Msamples/s through the block-streamed resample+low_pass+mix pipeline"
@@ -1106,6 +1143,7 @@ def side(args, argv, lite=False):
         return
     rh.async_status()
     head = rows[0]
+    dumped = dump_outputs(args.dump_outputs, {k_: f_() for k_, f_ in dumps.items()}) if args.dump_outputs and not lite else None
     if lite:  # a leg of the default line (roofline.side): the timing and the parity, no counter passes, nothing printed
         out_ = {"ms": head["kernel_ms"], "frac": head["frac"], "kernels": [{"kernel": r_["kernel"], "ms": r_["kernel_ms"], "frac": r_["frac"]} for r_ in rows], "workload": workload}
         if checks is not None:
@@ -1127,6 +1165,8 @@ def side(args, argv, lite=False):
                         "algorithmic_bytes_per_launch": head["algorithmic_bytes_per_launch"], "kernel_ms": head["kernel_ms"]}}
     if not args.no_cpu_baseline and checks is not None:
         res["parity"], res["cpu_baseline"] = checks()
+    if dumped is not None:
+        res["outputs"] = dumped
     emit(res)
 
 
@@ -1173,7 +1213,11 @@ def main():
     ap.add_argument("--baseline-sources", type=int, default=64, help="N > 1: sources of rank 0's shard the one-thread CPU baseline times")
     ap.add_argument("--one-gpu-value", type=float, default=None, help="Msamples/s of this bench at --gpus 1: an N > 1 run then prints multi_gpu.efficiency_vs_1gpu")
     ap.add_argument("--one-gpu-line", default=None, help="... or the 1-GPU JSON line itself / a file that holds it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32; a fixed sample of an output over its share of 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         self_spawn(args)  # (does not return)
     # The contract is ONE JSON line on stdout.  RCCL prints a version banner there from C (whatever NCCL_DEBUG says on this image), and other
