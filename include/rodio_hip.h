@@ -194,6 +194,31 @@ rh_status rh_channel_volume(float *dst, const float *src, size_t frames, uint32_
 rh_status rh_spatial_gains(const float emitter[3], const float left_ear[3],
                            const float right_ear[3], float out_gains[2]);
 
+/* ---- Parameters that change while a source plays: PeriodicAccess (src/source/periodic.rs:9-24,63-77) over
+ * Amplify::set_factor / set_log_factor (amplify.rs:27-35), ChannelVolume::set_volume (channel_volume.rs:71-88) and
+ * Spatial::set_positions (spatial.rs:48-69) -- what Player::append (player.rs:121-166) and SpatialPlayer::append
+ * (spatial_player.rs:60-77) wrap every source in.
+ * A parameter is a table of STEPS in device memory: sample `first + i` of the stream (counted where the parameter
+ * applies) takes entry (first + i) / period - first / period.  Bad arguments (a period of 0, fewer entries than the
+ * block reaches, out_ch > 16): RH_ERR_INVALID. */
+/* U of PeriodicAccess (periodic.rs:14-22): max(1, (period.as_secs_f32() * rate as f32 * channels as f32) as usize) --
+ * SAMPLES, not frames; the closure runs before sample 0, U, 2U, ... of the adapter's stream. */
+uint64_t rh_periodic_update_samples(uint64_t period_ns, uint32_t sample_rate, uint32_t channels);
+/* Amplify with a factor that changes every `period` samples: dst[i] = src[i] * factors_dev[step(i)] (amplify.rs:64),
+ * bit for bit rh_amplify with each step's factor.  Rows start anywhere; dst == src works in place. */
+rh_status rh_amplify_steps(float *dst, const float *src, size_t n, uint64_t first, uint64_t period,
+                           const float *factors_dev, uint32_t n_factors, rh_stream stream);
+/* ChannelVolume with gains that change every `gain_period` OUTPUT samples, optionally followed by Amplify with a
+ * factor that changes every `factor_period` (Spatial -> .. -> Amplify, the tail of a SpatialPlayer source, in one launch):
+ * out[j] = (m * gains_dev[step_g(j) * out_ch + j % out_ch]) * factors_dev[step_f(j)], m the frame's mean
+ * ((0 + s0) + s1 + ..) / in_ch, formed when the output frame begins; each output sample reads the gains of ITS step
+ * (channel_volume.rs:71-88: a change in mid-frame reaches the later channels of the frame).  factors_dev may be NULL (no
+ * factor).  Bit for bit rh_channel_volume with each step's gains, then rh_amplify_steps.  out_ch <= 16. */
+rh_status rh_channel_volume_steps(float *dst, const float *src, size_t frames, uint32_t in_ch, uint32_t out_ch,
+                                  uint64_t first, uint64_t gain_period, const float *gains_dev, uint32_t n_gains,
+                                  uint64_t factor_first, uint64_t factor_period, const float *factors_dev,
+                                  uint32_t n_factors, rh_stream stream);
+
 /* ---- reverb = Mix(x, Delay(Amplify(x))): src/source/mod.rs:628-634, delay.rs:8-16,68-75,
  * mix.rs:43-53.  delay_samples counts INTERLEAVED samples (delay.rs:14).  dst holds
  * n + delay_samples samples. */

@@ -1016,6 +1016,175 @@ private:
 };
 }  // namespace detail
 
+// ---------------------------------------------------------------- parameters that change while a source plays ----
+/// What a periodic_access() closure reaches (rodio's `inner_mut()`): views onto the adjustable stages in front of the access point.
+/// Amplify::set_factor / set_log_factor (amplify.rs:27-35).
+class LiveAmplify {
+public:
+    explicit LiveAmplify(std::vector<float> *v) : v_(v) {}
+    void set_factor(float factor) { (*v_)[0] = factor; }
+    void set_log_factor(float db) { (*v_)[0] = rh_db_to_linear(db); }
+    float factor() const { return (*v_)[0]; }
+
+private:
+    std::vector<float> *v_;
+};
+/// ChannelVolume::set_volume (channel_volume.rs:41-43).
+class LiveChannelVolume {
+public:
+    explicit LiveChannelVolume(std::vector<float> *v) : v_(v) {}
+    void set_volume(std::size_t channel, float volume) { v_->at(channel) = volume; }
+    float volume(std::size_t channel) const { return v_->at(channel); }
+    std::size_t channels() const { return v_->size(); }
+
+protected:
+    std::vector<float> *v_;
+};
+/// Spatial::set_positions (spatial.rs:48-69): the two gains of its ChannelVolume.
+class LiveSpatial : public LiveChannelVolume {
+public:
+    using LiveChannelVolume::LiveChannelVolume;
+    void set_positions(const float emitter[3], const float left_ear[3], const float right_ear[3]) {
+        float g[2];
+        check(rh_spatial_gains(emitter, left_ear, right_ear, g), "rh_spatial_gains");
+        (*v_)[0] = g[0];
+        (*v_)[1] = g[1];
+    }
+};
+class Controls;
+namespace detail {
+/// The schedule of a chain's periodic_access() closures and the values they set (GpuSource::periodic_access).  Every adjustable
+/// stage and access point of a chain counts the same samples (the stages between them hand on one sample per sample).  A stage
+/// that is about to compute samples [p, p + n) first has every closure called whose access lies in front of p + n (ensure()), in
+/// the order rodio calls them: by sample, and at one sample the access point further down the chain first (its next() runs its
+/// closure before it asks its input).  What a call sets holds from its access sample on (steps).
+struct LiveController {
+    enum Kind { Amplify = 0, ChannelVolume = 1, Spatial = 2 };
+    struct Param {
+        int kind;
+        std::size_t stage;       // the chain's stage that applies it
+        std::vector<float> cur;  // what the closures have set last
+        std::deque<std::pair<std::uint64_t, std::vector<float>>> steps;  // (first sample, values): the values from that sample on
+        std::size_t fused = SIZE_MAX;  // a channel volume: the amplify whose factor its launch applies
+    };
+    struct Access {
+        std::size_t stage;  // the access point's stage: it reaches the parameters of the stages in front of it
+        std::uint64_t U;    // rh_periodic_update_samples
+        std::function<void(Controls &)> fn;
+        std::uint64_t next = 0;  // the next access index to call
+    };
+    std::vector<Param> params;
+    std::vector<Access> accesses;
+    std::size_t first_stage = 0;  // the first adjustable stage or access point of the chain
+    std::uint64_t calls = 0;
+    void ensure(std::uint64_t end, bool inclusive);
+    // the table period of a parameter: gcd of the periods of the access points that reach it (no access point: one step for ever)
+    std::uint64_t period(const Param &p) const {
+        std::uint64_t g = 0;
+        for (const Access &a : accesses)
+            if (a.stage > p.stage) g = std::gcd(g, a.U);
+        return g ? g : (std::uint64_t)1 << 62;
+    }
+    static std::uint64_t steps_needed(std::uint64_t first, std::uint64_t period, std::uint64_t n) { return n ? (first + n - 1) / period - first / period + 1 : 0; }
+    // the values of samples [first, first + n) as a table of steps of `period` (rh_amplify_steps' layout).  `floor`: no stage computes a
+    // sample in front of it again (a seek goes back to the consumer's frame, never further): the steps in front of it go, so what is held
+    // stays within the pump's lookahead however long the stream plays.
+    void table(Param &p, std::uint64_t floor, std::uint64_t first, std::uint64_t period, std::uint64_t n, float *out) {
+        while (p.steps.size() > 1 && p.steps[1].first <= floor) p.steps.pop_front();
+        const std::uint64_t k = steps_needed(first, period, n), w = p.cur.size();
+        // (the scan starts at the step that holds at `first`)
+        std::size_t i = (std::size_t)(std::upper_bound(p.steps.begin(), p.steps.end(), first, [](std::uint64_t v, const std::pair<std::uint64_t, std::vector<float>> &st) { return v < st.first; }) -
+                                      p.steps.begin());
+        i = i ? i - 1 : 0;
+        for (std::uint64_t e = 0; e < k; ++e) {
+            const std::uint64_t s = std::max(first, (first / period + e) * period);
+            while (i + 1 < p.steps.size() && p.steps[i + 1].first <= s) ++i;
+            std::memcpy(out + e * w, p.steps[i].second.data(), w * sizeof(float));
+        }
+    }
+    std::size_t steps_held() const {
+        std::size_t n = 0;
+        for (const Param &p : params) n += p.steps.size();
+        return n;
+    }
+};
+/// A step table on its way to the device: written into one of two page-locked blocks (the other one may still be in a copy), copied
+/// on the chain's stream in front of the launch that reads it.
+struct LiveUpload {
+    PinnedBuf host[2];
+    void *done[2] = {nullptr, nullptr};
+    bool pending[2] = {false, false};
+    DeviceBuf dev;
+    int next = 0;
+    LiveUpload() {
+        for (void *&e : done) check(rh_event_create(&e), "rh_event_create");
+    }
+    LiveUpload(const LiveUpload &) = delete;
+    LiveUpload &operator=(const LiveUpload &) = delete;
+    ~LiveUpload() {
+        for (int i = 0; i < 2; ++i) {
+            if (pending[i]) (void)rh_event_synchronize(done[i]);
+            (void)rh_event_destroy(done[i]);
+        }
+    }
+    float *staging(std::size_t floats) {  // the block to write next: its previous copy has completed
+        if (pending[next]) check(rh_event_synchronize(done[next]), "rh_event_synchronize");
+        pending[next] = false;
+        host[next].reset(std::max<std::size_t>(floats, 16));
+        return host[next].get();
+    }
+    const float *upload(std::size_t floats, rh_stream s) {
+        dev.reset(std::max<std::size_t>(floats, 16));
+        check(rh_memcpy_h2d(dev.get(), host[next].get(), floats * sizeof(float), s), "rh_memcpy_h2d");
+        check(rh_event_record(done[next], s), "rh_event_record");
+        pending[next] = true;
+        next ^= 1;
+        return dev.get();
+    }
+};
+}  // namespace detail
+/// The argument of a periodic_access() closure: the adjustable stages in front of the access point, k-th of each kind in the chain's
+/// order (live_amplify, live_channel_volume, live_spatial), and the index of the access (call k runs before sample k * U).
+class Controls {
+public:
+    Controls(detail::LiveController *c, std::size_t stage, std::uint64_t index) : c_(c), stage_(stage), index_(index) {}
+    LiveAmplify amplify(std::size_t k = 0) { return LiveAmplify(find(detail::LiveController::Amplify, k)); }
+    LiveChannelVolume channel_volume(std::size_t k = 0) { return LiveChannelVolume(find(detail::LiveController::ChannelVolume, k)); }
+    LiveSpatial spatial(std::size_t k = 0) { return LiveSpatial(find(detail::LiveController::Spatial, k)); }
+    std::uint64_t access_index() const { return index_; }
+
+private:
+    std::vector<float> *find(int kind, std::size_t k) {
+        for (detail::LiveController::Param &p : c_->params)
+            if (p.stage < stage_ && p.kind == kind && k-- == 0) return &p.cur;
+        throw std::out_of_range("periodic_access: no such adjustable stage in front of the access point");
+    }
+    detail::LiveController *c_;
+    std::size_t stage_;
+    std::uint64_t index_;
+};
+inline void detail::LiveController::ensure(std::uint64_t end, bool inclusive) {
+    for (;;) {
+        Access *best = nullptr;
+        std::uint64_t at = 0;
+        for (Access &a : accesses) {
+            const std::uint64_t s = a.next * a.U;
+            if (s > end || (s == end && !inclusive)) continue;
+            if (!best || s < at || (s == at && a.stage > best->stage)) best = &a, at = s;
+        }
+        if (!best) return;
+        Controls c(this, best->stage, best->next);
+        best->fn(c);
+        ++best->next;
+        ++calls;
+        for (Param &p : params) {
+            if (p.stage >= best->stage || p.steps.back().second == p.cur) continue;
+            if (p.steps.back().first == at) p.steps.back().second = p.cur;
+            else p.steps.emplace_back(at, p.cur);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- GpuSource: adapter chain on one upstream ----
 /// `upstream.amplify(..).low_pass(..)...` with the chain executed block-wise on the GPU.  Adapters with
 /// memory (filters, limiter, AGC, reverb, converters) carry it across blocks: any block size gives the bits
@@ -1092,6 +1261,14 @@ public:
             if (st.span_rule) rule = st.span_rule;
         return rule == 2;
     }
+    /// `try_seek` of a chain with adjustable stages (live_*, periodic_access): the access counts go on from the consumer's position
+    /// (periodic.rs keeps its phase), so every stage from the first adjustable one to the end hands on one sample per sample.
+    bool live_seekable() const {
+        if (!live_) return true;
+        for (std::size_t k = live_->first_stage + 1; k < stages_.size(); ++k)
+            if (stages_[k].span_rule != 0) return false;
+        return true;
+    }
     /// `try_seek` through the chain, adapter by adapter as rodio does it: an adapter that cannot seek (reverb = Mix,
     /// mix.rs:116-120) fails the call before anything moved; otherwise the upstream seeks, what was pulled and processed
     /// ahead is dropped, and every adapter does to its state what its `try_seek` does -- filters and the limiter start
@@ -1100,6 +1277,7 @@ public:
     bool try_seek(Nanos pos) override {
         for (const Stage &st : stages_)
             if (!st.seekable) return false;
+        if (!live_seekable()) return false;
         if (!up_->try_seek(pos)) return false;
         reader_.restart();
         restart(ch_);
@@ -1626,6 +1804,80 @@ public:
     GpuSource &fade_in(Nanos duration) { return linear_gain_ramp(duration, 0.0f, 1.0f, false); }  // fadein.rs:11-13
     GpuSource &fade_out(Nanos duration) { return linear_gain_ramp(duration, 1.0f, 0.0f, true); }  // fadeout.rs:13
 
+    // -- adjustable stages and periodic_access (Player::append, player.rs:121-166; SpatialPlayer::append, spatial_player.rs:60-77).  The
+    // closures run on the thread that prepares a block (GpuMixer: a worker of its pool), at most about two blocks ahead of the consumer,
+    // one call per access index in increasing order; the values a call sets hold from its access sample on.
+    /// Amplify whose factor a periodic_access() closure behind it sets (amplify.rs:27-35,64).  Right behind a live_channel_volume /
+    /// live_spatial (access points in between) it runs inside that stage's launch.
+    GpuSource &live_amplify(float factor) {
+        detail::LiveController &lc = live_controller("live_amplify");
+        const std::size_t self = stages_.size();
+        std::size_t into = SIZE_MAX;  // the channel volume whose launch applies this factor
+        for (std::size_t i = lc.params.size(); i-- > 0;) {
+            const detail::LiveController::Param &p = lc.params[i];
+            if (p.kind == detail::LiveController::Amplify) break;
+            bool between = true;  // nothing but access points between the two
+            for (std::size_t k = p.stage + 1; k < self; ++k) between = between && stages_[k].passthrough;
+            if (between && p.fused == SIZE_MAX) into = i;
+            break;
+        }
+        lc.params.push_back(detail::LiveController::Param{detail::LiveController::Amplify, self, {factor}, {{0, {factor}}}});
+        const std::size_t me = lc.params.size() - 1;
+        auto pos = std::make_shared<std::uint64_t>(0);
+        std::shared_ptr<detail::LiveController> live = live_;
+        if (into != SIZE_MAX) {
+            lc.params[into].fused = me;
+            push([pos](Ctx &c) { *pos += c.n; return c.n; }).any_format();
+            stages_.back().passthrough = true;
+        } else {
+            auto up = std::make_shared<detail::LiveUpload>();
+            push([this, live, me, pos, up](Ctx &c) {
+                if (c.n) {
+                    live->ensure(*pos + c.n, false);
+                    detail::LiveController::Param &p = live->params[me];
+                    const std::uint64_t per = live->period(p), k = detail::LiveController::steps_needed(*pos, per, c.n);
+                    live->table(p, live_floor(*pos), *pos, per, c.n, up->staging(k));
+                    check(rh_amplify_steps(c.out, c.in, c.n, *pos, per, up->upload(k, c.stream), (std::uint32_t)k, c.stream), "rh_amplify_steps");
+                }
+                *pos += c.n;
+                return c.n;
+            }).any_format();
+        }
+        return live_stage_done(pos);
+    }
+    /// ChannelVolume whose gains a periodic_access() closure behind it sets (channel_volume.rs:41-43,71-88).  It changes the sample count,
+    /// so it is the chain's first adjustable stage or access point (RH_ERR_UNSUPPORTED otherwise).
+    GpuSource &live_channel_volume(std::vector<float> gains) { return live_cv(std::move(gains), detail::LiveController::ChannelVolume); }
+    /// Spatial whose positions a periodic_access() closure behind it sets (spatial.rs:26-69).
+    GpuSource &live_spatial(const float emitter[3], const float left_ear[3], const float right_ear[3]) {
+        float g[2];
+        check(rh_spatial_gains(emitter, left_ear, right_ear, g), "rh_spatial_gains");
+        return live_cv({g[0], g[1]}, detail::LiveController::Spatial);
+    }
+    /// `periodic_access(period, f)` (periodic.rs:9-24,63-77): f runs before sample 0, U, 2U, ... of the stream here, U =
+    /// rh_periodic_update_samples(period, rate, channels) of the format here, and reaches the adjustable stages in front through its
+    /// Controls.  Refused (RH_ERR_UNSUPPORTED) when a stage between an adjustable stage and this point does not hand on one sample per
+    /// sample (converters, uniform, reverb, delay, take_duration).  The count goes on across try_seek (rodio keeps the phase).
+    GpuSource &periodic_access(Nanos period, std::function<void(Controls &)> f) {
+        if (!f) throw std::invalid_argument("periodic_access: no closure");
+        detail::LiveController &lc = live_controller("periodic_access");
+        const std::size_t self = stages_.size();
+        lc.accesses.push_back(detail::LiveController::Access{self, rh_periodic_update_samples((std::uint64_t)period.count(), rate_, ch_), std::move(f)});
+        auto pos = std::make_shared<std::uint64_t>(0);
+        std::shared_ptr<detail::LiveController> live = live_;
+        push([live, pos](Ctx &c) {
+            live->ensure(*pos + c.n, c.flush);  // (the consumer's next() after the last sample reaches the access point once more: periodic.rs:63-77)
+            *pos += c.n;
+            return c.n;
+        }).any_format();
+        stages_.back().passthrough = true;
+        return live_stage_done(pos);
+    }
+    /// Calls of this chain's periodic_access() closures so far.
+    std::uint64_t periodic_calls() const { return live_ ? live_->calls : 0; }
+    /// Steps of the adjustable stages' values the chain holds (bounded by the pump's lookahead, whatever the stream's length).
+    std::size_t periodic_steps_held() const { return live_ ? live_->steps_held() : 0; }
+
 protected:
     void block_done() override {  // a bounded wait inside the limiter's scan expired (never seen on a healthy device): fail loudly
         if (scan_kernels_) check(rh_async_status(), "rh_async_status");
@@ -1737,7 +1989,7 @@ protected:
                 Ctx c{oth, cur, k, cap, run_ends, stream_};
                 k = st.run(c);
                 run_ends = run_ends || c.end;
-                std::swap(cur, oth);
+                if (!st.passthrough) std::swap(cur, oth);
             }
             ends = ends || run_ends;
             // the format of what came out: the adapters' own where one of them fixes it (or nothing changed), the run's otherwise
@@ -1836,6 +2088,7 @@ private:
         bool span_keeps_count = false;  // ... and it hands on one sample per sample until it ends the stream (take_duration): the input's spans lie where they lay
         // total_duration() behind the adapter from its input's (null: the input's, amplify.rs:95-97 and the like)
         std::function<std::optional<Nanos>(std::optional<Nanos>)> dur_fn = nullptr;
+        bool passthrough = false;  // the stage launches nothing and leaves its input where it is (an access point; an amplify fused into the launch in front)
     };
     // size_hint(): what every adapter makes of its input's answer.  `in(q)`: the input's size_hint() once q of ITS samples have been taken;
     // `emitted`: samples the adapter has emitted (both counted from the start of the stream, or from the last seek).  The state lives apart from
@@ -2128,6 +2381,84 @@ private:
             });
     }
 
+    // The chain's LiveController, created by its first adjustable stage or access point; every later one needs a chain of stages that
+    // hand on one sample per sample back to that first one (they all count the same samples).
+    detail::LiveController &live_controller(const char *who) {
+        if (!live_) {
+            live_ = std::make_shared<detail::LiveController>();
+            live_->first_stage = stages_.size();
+            return *live_;
+        }
+        for (std::size_t k = live_->first_stage + 1; k < stages_.size(); ++k)
+            if (stages_[k].span_rule != 0)
+                throw Error(RH_ERR_UNSUPPORTED, std::string("GpuSource::") + who + ": a stage between an adjustable stage or access point and this one does not hand on one sample per "
+                                                    "sample (a converter, uniform, reverb, delay, take_duration, channel_volume): the schedule of the closures would not follow it");
+        return *live_;
+    }
+    GpuSource &live_stage_done(std::shared_ptr<std::uint64_t> pos) {  // after try_seek the stage's count goes on at the consumer's position
+        return on_seek([this, pos](Nanos) { *pos = handed_out() - handed_out() % ch_; });
+    }
+    // the first sample any stage may compute again (a seek goes back to the consumer's frame): steps in front of it can go
+    std::uint64_t live_floor(std::uint64_t pos) const { return live_seekable() ? std::min<std::uint64_t>(pos, handed_out() - handed_out() % ch_) : pos; }
+    GpuSource &live_cv(std::vector<float> gains, int kind) {  // live_channel_volume / live_spatial
+        const std::uint16_t in_ch = ch_;
+        const std::uint16_t out_ch = (std::uint16_t)gains.size();
+        if (!out_ch) throw std::invalid_argument("live_channel_volume: no output channels");
+        if (gains.size() > 16) throw Error(RH_ERR_UNSUPPORTED, "live_channel_volume: more than 16 output channels");
+        // Every adjustable stage and access point of a chain counts the same samples; a channel volume counts ITS output, so it must come first
+        // (rodio's Player / SpatialPlayer chains put Spatial first).  In front of another adjustable stage or access point it would count
+        // other samples than they do: refused.
+        if (live_)
+            throw Error(RH_ERR_UNSUPPORTED, std::string("GpuSource::") + (kind == detail::LiveController::Spatial ? "live_spatial" : "live_channel_volume") +
+                                                ": behind another adjustable stage or access point (it changes the sample count: the adjustable stages would not count the same samples)");
+        detail::LiveController &lc = live_controller(kind == detail::LiveController::Spatial ? "live_spatial" : "live_channel_volume");
+        const std::size_t self = stages_.size();
+        lc.params.push_back(detail::LiveController::Param{kind, self, gains, {{0, gains}}});
+        const std::size_t me = lc.params.size() - 1;
+        auto pos = std::make_shared<std::uint64_t>(0);
+        auto rg = std::make_shared<Regroup>();
+        auto up = std::make_shared<detail::LiveUpload>(), upf = std::make_shared<detail::LiveUpload>();
+        std::shared_ptr<detail::LiveController> live = live_;
+        push([this, live, me, pos, rg, up, upf, in_ch, out_ch, self](Ctx &c) {
+            return run_grouped(c, in_ch, *rg, [&](const float *in, std::size_t n) {
+                const std::size_t frames = n / in_ch, m = frames * out_ch;
+                if (m) {
+                    const std::uint64_t floor = live_floor(*pos);
+                    live->ensure(*pos + m, false);
+                    detail::LiveController::Param &p = live->params[me];
+                    const std::uint64_t per = live->period(p), k = detail::LiveController::steps_needed(*pos, per, m);
+                    live->table(p, floor, *pos, per, m, up->staging(k * out_ch));
+                    const float *g = up->upload(k * out_ch, c.stream);
+                    const float *f = nullptr;
+                    std::uint64_t fper = 1, fk = 0;
+                    if (p.fused != SIZE_MAX) {  // ... and the factor of the live_amplify behind it, in the same launch
+                        detail::LiveController::Param &a = live->params[p.fused];
+                        fper = live->period(a);
+                        fk = detail::LiveController::steps_needed(*pos, fper, m);
+                        live->table(a, floor, *pos, fper, m, upf->staging(fk));
+                        f = upf->upload(fk, c.stream);
+                    }
+                    check(rh_channel_volume_steps(c.out, in, frames, in_ch, out_ch, *pos, per, g, (std::uint32_t)k, *pos, fper, f, (std::uint32_t)fk, c.stream), "rh_channel_volume_steps");
+                }
+                *pos += m;
+                if (n % in_ch) {  // (as channel_volume(): rodio's ChannelVolume asked again after its None returns a frame of its stale sum)
+                    for (std::size_t k = self + 1; k < stages_.size(); ++k)
+                        if (stages_[k].span_rule == 1)
+                            throw Error(RH_ERR_UNSUPPORTED, "GpuSource::live_channel_volume: its input ends inside a frame (channel_volume.rs:71-88)");
+                    stale_frame_ = true;
+                }
+                return m;
+            });
+        }, [in_ch, out_ch](std::size_t n) { return (n / in_ch + 1) * out_ch; }).on_seek([rg](Nanos) { rg->n = 0; })
+            .span_arithmetic(  // channel_volume.rs:103-105, as channel_volume()
+                [](std::optional<std::size_t> in, std::uint64_t) { return in; },
+                [in_ch, out_ch](std::uint64_t emitted) { return (emitted + out_ch - 1) / out_ch * in_ch; });
+        ch_ = out_ch;
+        may_cut_ = false;
+        return live_stage_done(pos);
+    }
+
+    std::shared_ptr<detail::LiveController> live_;  // adjustable stages / periodic_access (null: none)
     BoxSource up_;
     std::size_t block_frames_;
     std::uint16_t ch_ = 0;

@@ -26,6 +26,9 @@ from .source import (  # noqa: F401
     WavDecoder,
     WavDecoderChannels,
     agc_batch,
+    amplify_steps,
+    channel_volume_steps,
+    periodic_update_samples,
     async_status,
     agc_state,
     biquad_batch,

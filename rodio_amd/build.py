@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "librodio_hip.so")
-SOURCES = ["rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_limit.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip"]
+SOURCES = ["rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_limit.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip"]
 # -ffp-contract=off: the reference's f32 expressions (lerp, biquad, mixer sum) must not be
 # fused; kernels that want an FMA spell it __builtin_fmaf.
 # -fno-slp-vectorize: hipcc's SLP pass pairs the two stereo channels into v_pk_*_f32; on gfx950
@@ -63,6 +63,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if force or jobs or _stale(LIB, objs):
         run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs, "-ldl"])
     build_host_mirror_test(force, run)
+    build_live_test(force, run)
     return LIB
 
 
@@ -82,6 +83,25 @@ def build_host_mirror_test(force: bool, run) -> str:
     fake_exe = os.path.join(root, "tests", "cpp", "host_mirror_test_fake")
     if force or _stale(fake_exe, [src, fake_src, deps[1], deps[2]]):
         run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", os.path.join(root, "include"), src, fake_src, "-o", fake_exe])
+    return exe
+
+
+def build_live_test(force: bool, run) -> str:
+    """tests/cpp/live_test.cpp (chains with adjustable stages and periodic_access) against the library, and against
+    tests/cpp/fake_device.cpp + tests/cpp/fake_live.cpp (TEST INFRASTRUCTURE: the CPU stand-in, for the `-m "not gpu"` suite)."""
+    root = os.path.join(HERE, "..")
+    inc = os.path.join(root, "include")
+    src = os.path.join(root, "tests", "cpp", "live_test.cpp")
+    exe = os.path.join(root, "tests", "cpp", "live_test")
+    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h")]
+    gxx = shutil.which("g++") or "g++"
+    if force or _stale(exe, [src, LIB] + hdrs):
+        run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, src, "-L", HERE, "-lrodio_hip",
+             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
+    fakes = [os.path.join(root, "tests", "cpp", "fake_device.cpp"), os.path.join(root, "tests", "cpp", "fake_live.cpp")]
+    fake_exe = os.path.join(root, "tests", "cpp", "live_test_fake")
+    if force or _stale(fake_exe, [src] + fakes + hdrs):
+        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, src, *fakes, "-o", fake_exe])
     return exe
 
 

@@ -848,3 +848,43 @@ class ResampleLowpassMix:
             self.close()
         except Exception:
             pass
+
+
+# ---- parameters that change while a source plays (periodic.rs, amplify.rs:27-35, channel_volume.rs:71-88) ----------
+def periodic_update_samples(period_ns: int, sample_rate: int, channels: int) -> int:
+    """U of PeriodicAccess (periodic.rs:14-22): the closure runs before sample 0, U, 2U, ... -- samples, not frames."""
+    return int(lib.rh_periodic_update_samples(int(period_ns), int(sample_rate), int(channels)))
+
+
+def _table(values):
+    torch = _t()
+    if isinstance(values, torch.Tensor):
+        return values.to(device="cuda", dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32).ravel()).to("cuda")
+
+
+def amplify_steps(x, first: int, period: int, factors, out=None):
+    """rh_amplify_steps over the 1-D device tensor x: x[i] * factors[(first + i) // period - first // period].  `out` may be x
+    (in place) or any float32 view of the right length."""
+    _ensure()
+    f = _table(factors)
+    if out is None:
+        out = _dev_empty(x.numel())
+    check(lib.rh_amplify_steps(_ptr(out), _ptr(x), x.numel(), int(first), int(period), _ptr(f), f.numel(), _stream()), "rh_amplify_steps")
+    return out
+
+
+def channel_volume_steps(x, in_ch: int, out_ch: int, first: int, gain_period: int, gains, factor_first: int = 0, factor_period: int = 1,
+                         factors=None, out=None):
+    """rh_channel_volume_steps over the interleaved device tensor x (whole frames of in_ch): gains is [steps, out_ch]; output
+    sample j takes gains[step_g(j)][j % out_ch] and, with `factors`, then * factors[step_f(j)]."""
+    _ensure()
+    frames = x.numel() // in_ch
+    g = _table(gains)
+    f = _table(factors) if factors is not None else None
+    if out is None:
+        out = _dev_empty(frames * out_ch)
+    check(lib.rh_channel_volume_steps(_ptr(out), _ptr(x), frames, in_ch, out_ch, int(first), int(gain_period), _ptr(g), g.numel() // out_ch,
+                                      int(factor_first), int(factor_period), _ptr(f) if f is not None else None, f.numel() if f is not None else 0,
+                                      _stream()), "rh_channel_volume_steps")
+    return out

@@ -614,6 +614,71 @@ impl HintState {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ parameters that change while a source plays ----
+struct LiveParam { kind: u8, stage: usize, cur: Vec<f32>, steps: Vec<(u64, Vec<f32>)> }   // kind: 0 amplify, 1 channel volume, 2 spatial; steps: (first sample, values)
+struct LiveAccess { stage: usize, u: u64, f: Box<dyn FnMut(&mut Controls) + Send>, next: u64 }
+struct LiveState {
+    params: Vec<LiveParam>, accesses: Vec<LiveAccess>, calls: u64,
+    positions: Vec<Arc<std::sync::atomic::AtomicU64>>,   // every live stage's count: try_seek sets them to the consumer's frame (periodic.rs keeps its phase)
+    floor: u64,                                         // no stage computes a sample in front of this one again (u64::MAX: only the stage's own position bounds it)
+}
+/// The argument of a periodic_access() closure: the adjustable stages in front of the access point, k-th of each kind (rodio's inner_mut()).
+pub struct Controls<'a> { params: &'a mut Vec<LiveParam>, stage: usize, index: u64 }
+impl Controls<'_> {
+    fn find(&mut self, kind: u8, k: usize) -> &mut Vec<f32> {
+        let stage = self.stage;
+        &mut self.params.iter_mut().filter(|p| p.stage < stage && p.kind == kind).nth(k).expect("periodic_access: no such adjustable stage in front of the access point").cur
+    }
+    pub fn access_index(&self) -> u64 { self.index }
+    pub fn set_factor(&mut self, k: usize, factor: f32) { self.find(0, k)[0] = factor; }                                   // amplify.rs:27-30
+    pub fn set_log_factor(&mut self, k: usize, db: f32) { self.find(0, k)[0] = unsafe { rh_db_to_linear(db) }; }           // amplify.rs:33-35
+    pub fn set_volume(&mut self, k: usize, channel: usize, volume: f32) { self.find(1, k)[channel] = volume; }             // channel_volume.rs:41-43
+    pub fn set_positions(&mut self, k: usize, emitter: [f32; 3], left_ear: [f32; 3], right_ear: [f32; 3]) {              // spatial.rs:48-69
+        let mut g = [0f32; 2];
+        ck(unsafe { rh_spatial_gains(emitter.as_ptr(), left_ear.as_ptr(), right_ear.as_ptr(), g.as_mut_ptr()) }, "rh_spatial_gains");
+        self.find(2, k).copy_from_slice(&g);
+    }
+}
+impl Default for LiveState { fn default() -> Self { LiveState { params: Vec::new(), accesses: Vec::new(), calls: 0, positions: Vec::new(), floor: u64::MAX } } }
+impl LiveState {
+    fn position(&mut self) -> Arc<std::sync::atomic::AtomicU64> { let p = Arc::new(std::sync::atomic::AtomicU64::new(0)); self.positions.push(p.clone()); p }
+    /// Every closure whose access lies in front of `end` (at `end` too when `inclusive`: the consumer's ask after the last sample), by sample,
+    /// the access point further down the chain first at one sample.
+    fn ensure(&mut self, end: u64, inclusive: bool) {
+        loop {
+            let best = self.accesses.iter().enumerate().filter(|(_, a)| a.next * a.u < end || (inclusive && a.next * a.u == end))
+                .min_by_key(|(_, a)| (a.next * a.u, usize::MAX - a.stage)).map(|(i, _)| i);
+            let Some(i) = best else { return };
+            let (stage, at, index) = (self.accesses[i].stage, self.accesses[i].next * self.accesses[i].u, self.accesses[i].next);
+            (self.accesses[i].f)(&mut Controls { params: &mut self.params, stage, index });
+            self.accesses[i].next += 1;
+            self.calls += 1;
+            for p in self.params.iter_mut().filter(|p| p.stage < stage) {
+                if p.steps.last().unwrap().1 != p.cur { p.steps.push((at, p.cur.clone())); }
+            }
+        }
+    }
+    /// (period, table) of parameter `me` over samples [first, first + n): rh_amplify_steps' layout.
+    fn schedule(&mut self, me: usize, first: u64, n: u64) -> (u64, Vec<f32>) {
+        self.ensure(first + n, false);
+        let stage = self.params[me].stage;
+        let per = self.accesses.iter().filter(|a| a.stage > stage).fold(0u64, |g, a| gcd(g, a.u));
+        let per = if per == 0 { 1u64 << 62 } else { per };
+        let floor = first.min(self.floor);
+        let p = &mut self.params[me];
+        let gone = p.steps.iter().skip(1).take_while(|(f, _)| *f <= floor).count();   // (steps in front of the floor go: what is held stays within the lookahead)
+        p.steps.drain(..gone);
+        let k = if n == 0 { 0 } else { (first + n - 1) / per - first / per + 1 };
+        let mut out = Vec::with_capacity((k as usize) * p.cur.len());
+        for e in 0..k {
+            let s = first.max((first / per + e) * per);
+            out.extend_from_slice(&p.steps.iter().rev().find(|(f, _)| *f <= s).unwrap().1);
+        }
+        (per, out)
+    }
+}
+fn gcd(a: u64, b: u64) -> u64 { if b == 0 { a } else { gcd(b, a % b) } }
+
 // ------------------------------------------------------------------------------------------------ GpuSource ----
 struct Ctx<'a> { out: *mut f32, inp: *const f32, n: usize, out_cap: usize, flush: bool, stream: RhStream, pieces: &'a [Piece], end: bool }
 struct Stage {
@@ -642,6 +707,7 @@ pub struct GpuSource<I: Source> {
     durs: Vec<Option<Box<dyn Fn(Option<Duration>) -> Option<Duration> + Send>>>,   // total_duration() behind every adapter from its input's (None: the input's, amplify.rs:95-97 and the like)
     pulled_total: u64,             // samples pulled from the upstream, whatever was sought in between
     last_kind: u8,                 // the adapter pushed last: 1 a `uniform`, 2 a filter right behind a `uniform`, 0 anything else
+    live: Option<Arc<Mutex<LiveState>>>,   // adjustable stages / periodic_access (None: none)
 }
 type Arc<T> = std::sync::Arc<T>;
 type Mutex<T> = std::sync::Mutex<T>;
@@ -652,7 +718,7 @@ impl<I: Source> GpuSource<I> {
         let (ch, rate) = (upstream.channels().get(), upstream.sample_rate().get());
         GpuSource { up: upstream, block_frames: block_frames.max(1), ch, rate, in_ch: ch, in_rate: rate, stages: Vec::new(), reader: SpanReader::new(),
                     pieces: Vec::new(), span_aware: false, scan_kernels: false, may_cut: false, filter_mode: 0, a: DeviceBuf::new(), b: DeviceBuf::new(), pump: Pump::new(),
-                    hint: Arc::new(Mutex::new(HintState::default())), durs: Vec::new(), pulled_total: 0, last_kind: 0 }
+                    hint: Arc::new(Mutex::new(HintState::default())), durs: Vec::new(), pulled_total: 0, last_kind: 0, live: None }
     }
     /// `total_duration()` as rodio's adapters answer it, adapter by adapter: the input's behind the ones that keep it (amplify.rs:95-97,
     /// blt.rs:171-173, limit.rs:592-594, agc.rs:588-590, channel_volume.rs:119-121), plus the delay behind `delay` (delay.rs:111-115), the
@@ -985,6 +1051,88 @@ impl<I: Source> GpuSource<I> {
     }
     pub fn fade_in(self, duration: Duration) -> Self { self.linear_gain_ramp(duration, 0.0, 1.0, false) }   // fadein.rs:11-13
     pub fn fade_out(self, duration: Duration) -> Self { self.linear_gain_ramp(duration, 1.0, 0.0, true) }    // fadeout.rs:13
+
+    // -- adjustable stages and periodic_access (player.rs:121-166, spatial_player.rs:60-77); the C++ twin (rodio_hip.hpp) states the
+    // contract: one call per access index in increasing order, before any sample at or after k * U is computed, at most about two blocks
+    // ahead of the consumer.  (Here without the C++ twin's fused channel-volume + factor launch and its build-time refusals of a converter
+    // between adjustable stages; a step table goes up from pageable memory into a buffer of its own and the stage waits for its launch
+    // -- simpler than the C++ twin's page-locked staging, and it serialises the pump.)
+    fn live_state(&mut self) -> Arc<Mutex<LiveState>> { self.live.get_or_insert_with(|| Arc::new(Mutex::new(LiveState::default()))).clone() }
+    /// Amplify whose factor a periodic_access() closure behind it sets (amplify.rs:27-35,64).
+    pub fn live_amplify(mut self, factor: f32) -> Self {
+        let live = self.live_state();
+        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind: 0, stage: self.stages.len(), cur: vec![factor], steps: vec![(0, vec![factor])] }); (l.params.len() - 1, l.position()) };
+        self.push(move |c| {
+            let pos = at.load(std::sync::atomic::Ordering::Relaxed);
+            let (per, tab) = live.lock().unwrap().schedule(me, pos, c.n as u64);
+            let mut d = DeviceBuf::new();
+            d.reserve(tab.len());
+            ck(unsafe { rh_memcpy_h2d(d.p.cast(), tab.as_ptr().cast(), tab.len() * 4, c.stream) }, "rh_memcpy_h2d");
+            ck(unsafe { rh_amplify_steps(c.out, c.inp, c.n, pos, per, d.p, tab.len() as u32, c.stream) }, "rh_amplify_steps");
+            ck(unsafe { rh_stream_synchronize(c.stream) }, "rh_stream_synchronize");   // (d goes when the block's launch has run)
+            at.store(pos + c.n as u64, std::sync::atomic::Ordering::Relaxed);
+            c.n
+        }, |n, _| n, 0);
+        self
+    }
+    /// ChannelVolume whose gains a periodic_access() closure behind it sets (channel_volume.rs:41-43,71-88).
+    pub fn live_channel_volume(self, gains: Vec<f32>) -> Self { self.live_cv(gains, 1) }
+    /// Spatial whose positions a periodic_access() closure behind it sets (spatial.rs:26-69).
+    pub fn live_spatial(self, emitter: [f32; 3], left_ear: [f32; 3], right_ear: [f32; 3]) -> Self {
+        let mut g = [0f32; 2];
+        ck(unsafe { rh_spatial_gains(emitter.as_ptr(), left_ear.as_ptr(), right_ear.as_ptr(), g.as_mut_ptr()) }, "rh_spatial_gains");
+        self.live_cv(vec![g[0], g[1]], 2)
+    }
+    fn live_cv(mut self, gains: Vec<f32>, kind: u8) -> Self {
+        let (in_ch, out_ch) = (self.ch as usize, gains.len());
+        assert!(out_ch > 0 && out_ch <= 16, "live_channel_volume: 1 to 16 output channels");
+        assert!(self.live.is_none(), "live_channel_volume / live_spatial: the chain's first adjustable stage (it changes the sample count that the others count)");
+        let live = self.live_state();
+        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind, stage: self.stages.len(), cur: gains.clone(), steps: vec![(0, gains)] }); (l.params.len() - 1, l.position()) };
+        self.push(move |c| {
+            let pos = at.load(std::sync::atomic::Ordering::Relaxed);
+            let frames = c.n / in_ch;
+            let m = (frames * out_ch) as u64;
+            let (per, tab) = live.lock().unwrap().schedule(me, pos, m);
+            let mut d = DeviceBuf::new();
+            d.reserve(tab.len().max(1));
+            ck(unsafe { rh_memcpy_h2d(d.p.cast(), tab.as_ptr().cast(), tab.len() * 4, c.stream) }, "rh_memcpy_h2d");
+            ck(unsafe { rh_channel_volume_steps(c.out, c.inp, frames, in_ch as u32, out_ch as u32, pos, per, d.p, (tab.len() / out_ch) as u32, 0, 1, std::ptr::null(), 0, c.stream) }, "rh_channel_volume_steps");
+            ck(unsafe { rh_stream_synchronize(c.stream) }, "rh_stream_synchronize");
+            at.store(pos + m, std::sync::atomic::Ordering::Relaxed);
+            frames * out_ch
+        }, move |n, _| n / in_ch * out_ch, 2);
+        self.set_in_pos(move |e| (e + out_ch as u64 - 1) / out_ch as u64 * in_ch as u64);
+        self.ch = out_ch as u16;
+        self
+    }
+    /// `periodic_access(period, f)` (periodic.rs:9-24,63-77): f runs before sample 0, U, 2U, ... of the stream here (U =
+    /// rh_periodic_update_samples) and reaches the adjustable stages in front through its Controls.
+    pub fn periodic_access(mut self, period: Duration, f: impl FnMut(&mut Controls) + Send + 'static) -> Self {
+        let live = self.live_state();
+        let u = unsafe { rh_periodic_update_samples(period.as_nanos() as u64, self.rate, self.ch as u32) };
+        let at = { let mut l = live.lock().unwrap(); l.accesses.push(LiveAccess { stage: self.stages.len(), u, f: Box::new(f), next: 0 }); l.position() };
+        self.push(move |c| {
+            let pos = at.load(std::sync::atomic::Ordering::Relaxed);
+            live.lock().unwrap().ensure(pos + c.n as u64, c.flush);
+            at.store(pos + c.n as u64, std::sync::atomic::Ordering::Relaxed);
+            if c.n > 0 { ck(unsafe { rh_memcpy_d2d(c.out.cast(), c.inp.cast(), c.n * 4, c.stream) }, "rh_memcpy_d2d"); }
+            c.n
+        }, |n, _| n, 0);
+        self
+    }
+    /// `try_seek` of a chain with adjustable stages: the access counts go on from the consumer's position, so every stage behind the
+    /// first adjustable one hands on one sample per sample.
+    pub fn live_seekable(&self) -> bool {
+        let Some(l) = self.live.as_ref() else { return true };
+        let l = l.lock().unwrap();
+        let first = l.params.iter().map(|p| p.stage).chain(l.accesses.iter().map(|a| a.stage)).min().unwrap_or(0);
+        self.stages.iter().skip(first + 1).all(|s| s.span_rule == 0)
+    }
+    /// Calls of this chain's periodic_access() closures so far.
+    pub fn periodic_calls(&self) -> u64 { self.live.as_ref().map_or(0, |l| l.lock().unwrap().calls) }
+    /// Steps of the adjustable stages' values the chain holds (bounded by the lookahead).
+    pub fn periodic_steps_held(&self) -> usize { self.live.as_ref().map_or(0, |l| l.lock().unwrap().params.iter().map(|p| p.steps.len()).sum()) }
     /// `take_duration(d)`, with `set_filter_fadeout()` when `fade_out` (take.rs:96-148).  `try_seek` starts the duration over from the new
     /// position: what is left is the requested duration less `pos` (take.rs:222-231).
     pub fn take_duration(mut self, duration: Duration, fade_out: bool) -> Self {
@@ -1060,6 +1208,10 @@ impl<I: Source> BlockSource for GpuSource<I> {
         // the slot's page-locked block is about to be rewritten: the copy that read it two blocks ago must have run (a consumer that takes the
         // blocks on the device never waits on the host -- see GpuSource::enqueue in include/rodio_hip.hpp)
         if self.pump.device_out { ck(unsafe { rh_event_synchronize(self.pump.slot[i].done.0) }, "rh_event_synchronize"); }
+        if let Some(l) = self.live.as_ref() {   // the first sample a seek can go back to: the consumer's frame
+            let (h, ch, seekable) = (self.pump.handed_out, self.ch as u64, self.live_seekable());
+            l.lock().unwrap().floor = if seekable { h - h % ch } else { u64::MAX };
+        }
         self.pump.slot[i].stage.reserve(want);
         { let h = self.up.size_hint(); self.hint.lock().unwrap().log.note(self.pulled_total, h); }   // (size_hint(): what the upstream answers where this block's first sample is pulled)
         let (mut n, flush);
@@ -1159,11 +1311,16 @@ impl<I: Source> Source for GpuSource<I> {
     /// every adapter does to its state what its `try_seek` does (blt.rs:350-377, limit.rs:1139-1158, linear_ramp.rs:141-146).
     fn try_seek(&mut self, pos: Duration) -> Result<(), SeekError> {
         if self.stages.iter().any(|s| !s.seekable) { return Err(SeekError::NotSupported { underlying_source: "rodio_hip::GpuSource (reverb / delay in the chain)" }); }
+        if !self.live_seekable() { return Err(SeekError::NotSupported { underlying_source: "rodio_hip::GpuSource (a converter behind periodic_access)" }); }
         self.up.try_seek(pos)?;
         self.reader.restart();
         let ch = self.ch as usize;
         self.pump.restart(ch);
         for st in &mut self.stages { if let Some(f) = st.on_seek.as_mut() { f(pos); } }
+        if let Some(l) = self.live.as_ref() {   // the access counts go on from the consumer's frame
+            let h = self.pump.handed_out;
+            for p in &l.lock().unwrap().positions { p.store(h - h % ch as u64, std::sync::atomic::Ordering::Relaxed); }
+        }
         {   // (the adapters' counts start over: what the chain emits from here on is the stream behind the new position, less the samples that keep the consumer's channel)
             let mut h = self.hint.lock().unwrap();
             h.log.clear();
