@@ -21,10 +21,21 @@ void set_hip_error(hipError_t e, const char *what);
 // process that changes one afterwards calls rh_init() again.  knob() returns the value or nullptr.
 enum Knob {
     K_AGC_SEQ, K_AGC_VEC, K_BIQUAD_NO_FALLBACK, K_BIQUAD_SEQ, K_BIQUAD_R, K_BIQUAD_NW, K_BIQUAD_WGS, K_LIMIT_SEQ, K_LIMIT_R, K_LIMIT_NW, K_LIMIT_WGS, K_LIMIT_GRID,
-    K_LIMIT_SKEW, K_LIMIT_NIO, K_LIMIT_INIT, K_SCAN_DMA_TOP, K_SCAN_SPIN_LIMIT, K_NO_HYBRID, K_NO_TICKET_SHARDS, K_PROF_DUMP, K_HOST_ALLOC, K_NO_MIX_FIRST, K_MIX_U, K_NO_CHUNK, K_CHUNK_HALF, K_AUTOTUNE_LOG, K_RAG_RESIDENT, K_RAG_TWO_KERNELS, K_AGC_SEGMENTS, K_RS_PIPE, K_DASP_I64_VIA_F64, K_MIX_GROUPS, K_CLASSES_SIDE_BY_SIDE, K_AGC_FUSED_R4, K_STREAM_UPLOAD_ALWAYS, K_STREAM_NO_REJOIN, K_NO_SBLK, K_SBLK_KV, K_SBLK_NO_OVERLAP, K_CLASSES_ONE_BY_ONE, K_CLASSES_ONE_WAVE, K_WIDE_GENERAL, K_PCM_NO_TILE, K_PCM_TILE_KB, K_LERP_IEEE_DIV, K_COUNT
+    K_LIMIT_SKEW, K_LIMIT_NIO, K_LIMIT_INIT, K_SCAN_DMA_TOP, K_SCAN_SPIN_LIMIT, K_NO_HYBRID, K_NO_TICKET_SHARDS, K_PROF_DUMP, K_HOST_ALLOC, K_NO_MIX_FIRST, K_MIX_U, K_NO_CHUNK, K_CHUNK_HALF, K_AUTOTUNE_LOG, K_RAG_RESIDENT, K_RAG_TWO_KERNELS, K_AGC_SEGMENTS, K_RS_PIPE, K_DASP_I64_VIA_F64, K_MIX_GROUPS, K_CLASSES_SIDE_BY_SIDE, K_AGC_FUSED_R4, K_STREAM_UPLOAD_ALWAYS, K_STREAM_NO_REJOIN, K_NO_SBLK, K_SBLK_KV, K_SBLK_NO_OVERLAP, K_CLASSES_ONE_BY_ONE, K_CLASSES_ONE_WAVE, K_WIDE_GENERAL, K_PCM_NO_TILE, K_PCM_TILE_KB, K_LERP_IEEE_DIV, K_COUNTER_JUMP, K_STREAM_START, K_COUNT
 };
 const char *knob(Knob k);
 void load_knobs();
+// RH_COUNTER_JUMP=<after>:<tickets_left>:<launches_left>, parsed by load_knobs: the 32-bit counters that live across launches
+// are moved forward, as though the launches in between had run, to a few steps before their wrap -- a fused-path handle when it takes its
+// after-th epoch tag (rhp::next_epoch), the scan kernels (rh_limit, rh_biquad mode 1) at their after-th launch since rh_init.  Ticket
+// counters then hand out 2^32 - tickets_left before they wrap, an epoch tag launches_left tags before its re-base.  Unset: on == false.
+struct CounterJump {
+    bool on;
+    uint32_t after, tickets_left, launches_left;
+};
+const CounterJump &counter_jump();
+// The scan kernels' side of it: true for exactly the after-th launch since rh_init (counted by the calls that ask)
+bool scan_jump_due();
 
 #define RH_HIP_TRY(expr)                                   \
     do {                                                   \
@@ -64,6 +75,8 @@ inline hipError_t fill_now(void *p, int value, size_t bytes) {
 // A fill ON a stream, by a kernel of this library (rh_runtime.hip): whatever initialises state that a later kernel reads is
 // ordered the way kernels are (hipMemsetAsync was part of the limiter's wrong-state flake, rh_limit.hip, k_limit_init).
 hipError_t fill_async(void *p, int value, size_t bytes, hipStream_t s);
+// ctl[0] += d_ticket and ctl[32 * (1 + x)] += d_shards for x < n_shards, as a launch on `s` (RH_COUNTER_JUMP)
+hipError_t counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uint32_t d_shards, hipStream_t s);
 
 // Scratch memory for one launch on stream `s`: a buffer owned by the library, one per stream, grown on demand (which waits
 // for the stream once) and reused by every later launch on that stream -- launches on a stream run one after the other, so

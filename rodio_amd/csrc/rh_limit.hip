@@ -1213,6 +1213,12 @@ extern "C" rh_status rh_limit(float *dst, const float *src, uint64_t frames, uin
     a.gran = reinterpret_cast<float *>(scratch + head + (state ? 0 : aux->parity) * gran_bytes);
     a.gran_other = state ? nullptr : reinterpret_cast<float *>(scratch + head + (aux->parity ^ 1u) * gran_bytes);
     a.ticket_base = aux->ticket_base;
+    if (rh::scan_jump_due()) {  // RH_COUNTER_JUMP: the counter moves on as though launches had taken the tickets in between (the wrap then falls inside this launch)
+        const uint32_t d = (0u - rh::counter_jump().tickets_left) - aux->ticket_base;
+        if (e == hipSuccess) e = rh::counters_add(a.ctl, d, 0, 0, s);
+        aux->ticket_base += d;
+        a.ticket_base = aux->ticket_base;
+    }
     if (state) a.state_in = snap, a.state_out = state;
     if (e == hipSuccess) {
         static int occupancy[sizeof(kVariants) / sizeof(kVariants[0])];  // asked once per variant (both instantiations share registers and LDS)

@@ -104,7 +104,8 @@ __global__ __launch_bounds__(64, (R <= 4 ? (KV <= 5 ? 5 : 4) : R <= 6 ? 3 : R <=
     const uint32_t m_tile0 = tile * L;
     const uint32_t m0 = m_tile0 + (uint32_t)lane * R;
     const uint64_t mg0 = p.st_mode ? p.st_m0 : 0;  // block streaming: this launch starts at global output frame st_m0
-    const bool first = (mg0 + m0 == 0);  // stream start: x'[-1] = x'[-2] = 0
+    const uint64_t mfirst = p.st_mode ? p.st_mfirst : 0;
+    const bool first = (mg0 + m0 == mfirst);  // stream start: x'[-1] = x'[-2] = 0
     const uint32_t Mout = (uint32_t)p.out_frames;
     const uint32_t Ns = p.eq_frames;  // every source has Ns frames (and Mout output frames)
     const uint64_t g0 = p.st_mode ? p.st_g0 : 0;  // ... and the buffers start at global input frame st_g0
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(64, (R <= 4 ? (KV <= 5 ? 5 : 4) : R <= 6 ? 3 : R <=
     {
         const uint32_t dthr = Ns - 1 - i_base;
         const int thr = (int)((dthr < (1u << 27) ? dthr : (1u << 27)) * FB);
-        Cursor c = cursor_at(first ? 0 : mg0 + m0 - 2, p);
+        Cursor c = cursor_at(first ? mfirst : mg0 + m0 - 2, p);
 #pragma unroll
         for (int rr = 0; rr < R + 2; ++rr) {
             const bool dummy = first && rr < 2;
@@ -641,7 +642,8 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
     const uint32_t m0 = m_tile0 + (uint32_t)lane * R;
     const uint64_t mg0 = p.st_mode ? p.st_m0 : 0;  // block streaming: this launch starts at global output frame st_m0 ...
     const uint64_t g0 = p.st_mode ? p.st_g0 : 0;   // ... and the buffers start at global input frame st_g0
-    const bool first = (mg0 + m0 == 0);  // stream start: x'[-1] = x'[-2] = 0
+    const uint64_t mfirst = p.st_mode ? p.st_mfirst : 0;
+    const bool first = (mg0 + m0 == mfirst);  // stream start: x'[-1] = x'[-2] = 0
     const uint32_t Mout = (uint32_t)p.out_frames;
     const uint32_t col = tile + p.col0;  // this tile's column in the per-source aggregate rows
     const uint32_t ncol = p.gran_cols;
@@ -680,7 +682,7 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
     int offA[R + 2];
     float wgt[R + 2];
     {
-        Cursor c = cursor_at(first ? 0 : mg0 + m0 - 2, p);
+        Cursor c = cursor_at(first ? mfirst : mg0 + m0 - 2, p);
 #pragma unroll
         for (int rr = 0; rr < R + 2; ++rr) {
             const bool dummy = first && rr < 2;
@@ -2942,12 +2944,9 @@ rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint
         if (w != RH_OK) return w;
     }
     const Plan &pl = *p->plan;
-    p->epoch += 1;
-    if (p->epoch == 0) {  // tag wrap: old tags could alias, start over from a clean table
-        if (p->d_gran) RH_HIP_TRY(hipMemsetAsync(p->d_gran, 0, p->gran_words * 8, s));
-        if (p->chunk.d_halo) RH_HIP_TRY(hipMemsetAsync(p->chunk.d_halo, 0, p->chunk.cap_tiles * 64, s));
-        if (p->chunk.d_gran) RH_HIP_TRY(hipMemsetAsync(p->chunk.d_gran, 0, p->chunk.cap_tiles * 32, s));
-        p->epoch = 1;
+    {
+        const rh_status w = next_epoch(p, s);
+        if (w != RH_OK) return w;
     }
     Params k;
     k.srcs = p->d_srcs + first;
@@ -2982,6 +2981,7 @@ rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint
     k.st_active = sa.active;
     k.st_m0 = sa.m0;
     k.st_g0 = sa.g0;
+    k.st_mfirst = sa.mode ? p->st_mfirst : 0;
     k.st_win = sa.win;
     k.st_wout = sa.wout;
     k.gran_cols = sa.gran_cols ? sa.gran_cols : p->n_tiles;

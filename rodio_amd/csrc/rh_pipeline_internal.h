@@ -98,6 +98,7 @@ struct Params {
     // k_rlm_fast, block streaming (st_mode: 0 off, 1 block of a running stream, 2 its last block):
     uint32_t st_mode, st_active;  // st_active: output frames this block emits (a multiple of R in mode 1)
     uint64_t st_m0, st_g0;        // global index of the block's first output frame / of input frame 0 of the buffers
+    uint64_t st_mfirst;           // ... and of the stream's first output frame (0 unless RH_STREAM_START): x'[-1] = x'[-2] = 0 in front of it
     // k_rlm_wave keeps one aggregate row per source: gran_cols columns, tile t in column t + col0.  Streaming sets
     // col0 = 1: column 0 then holds the source's filter state at the block start, i.e. the aggregate of a virtual
     // predecessor tile -- the look-back needs no other change.
@@ -263,12 +264,14 @@ struct rh_rlm {
     unsigned long long *d_prof = nullptr;
     uint32_t n_sources = 0, n_tiles = 0;
     uint64_t out_frames = 0;
-    uint32_t epoch = 0;
+    uint32_t epoch = 0;     // the tag of the last launch's words (rhp::next_epoch: 0 < epoch <= kEpochLimit)
+    uint32_t n_epochs = 0;  // tags taken (RH_COUNTER_JUMP counts them)
     uint32_t ticket_base = 0;
     uint32_t shard_base = 0;  // batch mode with sharded ticket counters (d_ctl + 32*(1+x)): tickets each of them has handed out
     // block streaming (rh_rlm_stream_*)
     bool st_on = false, st_done = false;
     uint64_t st_g0 = 0, st_m = 0;
+    uint64_t st_mfirst = 0;  // output frame the stream started at (RH_STREAM_START; else 0)
     uint64_t st_chunk_in = 0, st_chunk_out = 0;  // a stream of spanned sources: input / output frames per span (0: continuous)
     uint32_t st_nsrc = 0;
     float *d_w[2] = {nullptr, nullptr};
@@ -363,6 +366,21 @@ void sblk_free(rh_rlm *p);
 void sblk_other_block(rh_rlm *p, bool stream_begins = false);
 uint32_t sblk_chained_blocks(const rh_rlm *p);  // blocks of the current stream launched without a barrier behind the block in front  // a block of the stream ran elsewhere (or the stream begins)
 // rh_pipeline_plan.hip
+// The epoch tag of the handle's tables ({tag, f32} words: d_gran, the k_rlm_chunk halo / aggregates, k_rlm_sblk's sets and hand-off words).
+// Every launch takes the next tag; tag 0 means "never written".  Words live across launches too: column 0 of a per-source stream's rows
+// (the states, tagged for the launch that comes next) and k_rlm_sblk's hand-off words.  So the tag never wraps: when it reaches kEpochLimit,
+// every word of the tables is RE-BASED on the stream in front of the next launch -- tag t > kEpochShift becomes t - kEpochShift, every older
+// tag 0 -- and the epoch moves down by kEpochShift.  The live words keep their tags relative to the epoch, and no word is older than the
+// epoch plus one, so a later tag never matches a stale word.  *launched: a kernel was queued in front of the next launch (it needs a barrier).
+constexpr uint32_t kEpochLimit = 0xfffffff0u, kEpochShift = 0x80000000u;
+rh_status next_epoch(rh_rlm *p, hipStream_t s, bool *launched = nullptr);
+// On `s`, for every word of w[0, n) with tag t != 0: t in [lo, hi] becomes t - sub; t < lo becomes 0 if zero_below (else stays)
+struct Retag {
+    uint32_t lo, hi, sub;
+    bool zero_below;
+};
+hipError_t launch_retag(unsigned long long *w, size_t n, const Retag &r, hipStream_t s);
+void sblk_retag(rh_rlm *p, hipStream_t s, const Retag &r);
 rh_status wait_idle(rh_rlm *p);
 rh_status pre_launch(rh_rlm *p, hipStream_t s);
 rh_status mark_launch(rh_rlm *p, hipStream_t s);

@@ -48,6 +48,60 @@ rh_status mark_launch(rh_rlm *p, hipStream_t s) {
     return RH_OK;
 }
 
+}  // namespace rhp
+namespace {
+__global__ void k_retag(unsigned long long *w, size_t n, uint32_t lo, uint32_t hi, uint32_t sub, uint32_t zero_below) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const unsigned long long v = w[i];
+        const uint32_t t = (uint32_t)(v >> 32);
+        if (t == 0 || t > hi || (t < lo && !zero_below)) continue;
+        const uint32_t u = t >= lo ? t - sub : 0u;
+        w[i] = u ? ((unsigned long long)u << 32) | (v & 0xffffffffull) : 0ull;
+    }
+}
+}  // namespace
+namespace rhp {
+hipError_t launch_retag(unsigned long long *w, size_t n, const Retag &r, hipStream_t s) {
+    if (!w || !n) return hipSuccess;
+    hipLaunchKernelGGL(k_retag, dim3(rh::grid_for(n)), dim3(256), 0, s, w, n, r.lo, r.hi, r.sub, r.zero_below ? 1u : 0u);
+    return hipGetLastError();
+}
+static rh_status retag_tables(rh_rlm *p, hipStream_t s, const Retag &r) {
+    RH_HIP_TRY(launch_retag(p->d_gran, p->gran_words, r, s));
+    RH_HIP_TRY(launch_retag(p->chunk.d_halo, p->chunk.cap_tiles * 8, r, s));
+    RH_HIP_TRY(launch_retag(p->chunk.d_gran, p->chunk.cap_tiles * 4, r, s));
+    sblk_retag(p, s, r);
+    RH_CHECK_LAUNCH();
+    return RH_OK;
+}
+// The one place where the epoch moves (see rh_pipeline_internal.h); in front of the launch that takes the new tag, on its stream.
+rh_status next_epoch(rh_rlm *p, hipStream_t s, bool *launched) {
+    if (launched) *launched = false;
+    const rh::CounterJump &j = rh::counter_jump();
+    if (j.on && ++p->n_epochs == j.after) {  // RH_COUNTER_JUMP: every counter of the handle as though the launches in between had run
+        const uint32_t to = 0u - j.tickets_left;
+        const uint32_t dt = to - p->ticket_base, ds = to - p->shard_base;
+        RH_HIP_TRY(rh::counters_add(p->d_ctl, dt, 8u, ds, s));
+        p->ticket_base += dt;
+        p->shard_base += ds;
+        const uint32_t target = kEpochLimit - (j.launches_left < kEpochLimit - 1 ? j.launches_left : kEpochLimit - 1);
+        if (target > p->epoch) {  // the words that wait for the next launch move with the epoch; the older ones keep their (now stale) tags
+            const rh_status st = retag_tables(p, s, Retag{p->epoch + 1u, p->epoch + 1u, p->epoch - target, false});
+            if (st != RH_OK) return st;
+            p->epoch = target;
+        }
+        if (launched) *launched = true;
+    }
+    if (p->epoch >= kEpochLimit) {  // the re-base
+        const rh_status st = retag_tables(p, s, Retag{kEpochShift + 1u, 0xffffffffu, kEpochShift, true});
+        if (st != RH_OK) return st;
+        p->epoch -= kEpochShift;
+        if (launched) *launched = true;
+    }
+    p->epoch += 1;
+    return RH_OK;
+}
+
 // Predecessor tiles a tile of L frames has to look back at: ||B^(L*J)|| < 2^-40 (older history is
 // below f32 resolution of the state); 0 = pole radius too close to 1 for this tile length.
 uint32_t look_tiles(const M2 &B, uint64_t L) {

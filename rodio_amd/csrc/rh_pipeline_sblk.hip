@@ -550,7 +550,6 @@ struct SblkPlan {
     bool last_handed = false;              // ... if it leaves one (a block of a running stream under rh_rlm_stream_overlap)
     hipStream_t last_stream = nullptr;     // the stream the block in front was launched on
     uint32_t n_chained = 0;                // blocks launched without a barrier behind the block in front (diagnostics)
-    uint32_t blk = 0;                      // blocks of the current stream that this kernel ran
     bool prev_sblk = false;                // ... and the block before this one was one of them
     uint64_t seen_version = ~0ull;         // the source table the block in front read (a block behind a new upload starts behind a barrier)
 };
@@ -560,6 +559,15 @@ void sblk_other_block(rh_rlm *p, bool stream_begins) {  // a block of the stream
     if (!s) return;
     s->prev_sblk = false;
     if (stream_begins) s->n_chained = 0;
+}
+
+void sblk_retag(rh_rlm *p, hipStream_t hs, const Retag &r) {  // (next_epoch: the re-base and RH_COUNTER_JUMP; the caller checks the launches)
+    SblkPlan *s = static_cast<SblkPlan *>(p->sblk);
+    if (!s) return;
+    (void)launch_retag(s->d_gran, 3 * s->cap_tiles * 4, r, hs);
+    (void)launch_retag(s->d_hand, s->d_hand ? 3 * 4 : 0, r, hs);
+    const uint32_t t = s->last_tag;
+    if (t && t <= r.hi && (t >= r.lo || r.zero_below)) s->last_tag = t >= r.lo ? t - r.sub : 0u;
 }
 
 uint32_t sblk_chained_blocks(const rh_rlm *p) {
@@ -723,7 +731,7 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
     // table (nothing of ours was queued in between), and left the tagged state.  Three sets of hand-off tables in rotation: block k + 2 starts
     // on an XCD only when block k + 1 is done there, and block k + 1's tiles there looked back at tiles of the other XCDs, which started behind
     // block k's (tiles >= 16: every XCD holds a tile that looks back across all eight) -- the third set is slack on top of that argument.
-    const int set = (int)(s.blk % 3u);
+    const int set = (s.last_set + 1) % 3;  // (the next set of the rotation: a count of blocks taken mod 3 repeats a set where the count wraps)
     if (ovl && !s.d_hand) {
         RH_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_hand), 3 * 4 * sizeof(unsigned long long)));
         RH_HIP_TRY(rh::fill_now(s.d_hand, 0, 3 * 4 * sizeof(unsigned long long)));  // tag 0 = never written
@@ -733,13 +741,11 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
         const rh_status w = pre_launch(p, hs);
         if (w != RH_OK) return w;
     }
-    p->epoch += 1;
-    if (p->epoch == 0) {  // tag wrap: start over from clean tables
-        if (p->d_gran) RH_HIP_TRY(hipMemsetAsync(p->d_gran, 0, p->gran_words * 8, hs));
-        RH_HIP_TRY(hipMemsetAsync(s.d_gran, 0, 3 * s.cap_tiles * 32, hs));
-        if (s.d_hand) RH_HIP_TRY(hipMemsetAsync(s.d_hand, 0, 3 * 4 * sizeof(unsigned long long), hs));
-        chained = false;  // (behind the fills, and no tag of the old count is waited for)
-        p->epoch = 1;
+    {
+        bool queued = false;
+        const rh_status w = next_epoch(p, hs, &queued);
+        if (w != RH_OK) return w;
+        if (queued) chained = false;  // (behind the re-tag: it must not run beside this block)
     }
     Params k;
     std::memset(&k, 0, sizeof k);
@@ -768,12 +774,13 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
     k.st_active = (uint32_t)out;
     k.st_m0 = sa.m0;
     k.st_g0 = sa.g0;
+    k.st_mfirst = p->st_mfirst;
     k.st_win = sa.win;
     k.st_wout = sa.wout;
     k.u = s.uni;
     SblkArgs q;
     {
-        const uint64_t mb = sa.m0 >= 2 ? sa.m0 - 2 : 0;
+        const uint64_t mb = sa.m0 - std::min<uint64_t>(2, sa.m0 - p->st_mfirst);  // (fewer than two frames in front of the stream's first)
         const unsigned __int128 pp = (unsigned __int128)mb * F;
         const uint64_t ib_g = (uint64_t)(pp / T);
         if (ib_g < sa.g0) return RH_OK;  // (the rows start behind the first tap of frame m0 - 2: not a block of this stream's own making)
@@ -806,7 +813,6 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
     s.seen_version = p->srcs_version;
     if (chained) s.n_chained += 1;
     s.prev_sblk = true;
-    s.blk += 1;
     if (!direct) p->shard_base += grid / 8u;
     p->n_tiles = (uint32_t)tiles;
     *taken = true;

@@ -59,6 +59,12 @@ rh_status rh_rlm_stream_begin(rh_rlm *p) {
     p->st_on = true;
     p->st_done = false;
     p->st_g0 = p->st_m = 0;
+    if (const char *k = rh::knob(rh::K_STREAM_START)) {  // long-running tests: the stream starts k periods of the converter in --
+        const uint64_t n = strtoull(k, nullptr, 10);     // k spans of st_chunk_in input frames, else k * F input / k * T output frames of the
+        const uint64_t fi = p->st_chunk_in ? p->st_chunk_in : p->F, fo = p->st_chunk_in ? p->st_chunk_out : p->T;  // reduced ratio, where the
+        if (n && n < (1ull << 40) / (fi > fo ? fi : fo)) p->st_g0 = n * fi, p->st_m = n * fo;  // converter's arithmetic is what it is at 0
+    }
+    p->st_mfirst = p->st_m;
     p->st_nsrc = 0;
     p->st_cur = 0;
     p->st_total.clear();
@@ -340,7 +346,10 @@ static rh_status stream_block_v_impl(rh_rlm *p, const float *const *srcs_host, c
             }
             launch_state_sum(hs, p->d_gran, p->d_srcs, n_sources, p->st_cols, p->epoch + 1, p->d_w[p->st_cur]);  // (column 0 carries the tag of the launch that would have read it)
             RH_CHECK_LAUNCH();
-            p->epoch += 1;  // ... a tag the summed launch that comes next must not share: its tiles' words lie in the same table
+            {  // ... a tag the summed launch that comes next must not share: its tiles' words lie in the same table
+                const rh_status ne = next_epoch(p, hs);
+                if (ne != RH_OK) return ne;
+            }
             {
                 const rh_status mk = mark_launch(p, hs);
                 if (mk != RH_OK) return mk;
@@ -405,10 +414,6 @@ static rh_status stream_block_v_impl(rh_rlm *p, const float *const *srcs_host, c
         }
         p->st_cols = (uint32_t)cols;
         p->st_total.assign(n_sources, ~0ull);
-        if (p->filt && p->epoch >= 0xf0000000u) {  // keep the epoch tag from wrapping inside a stream (its states live in the table)
-            RH_HIP_TRY(hipMemsetAsync(p->d_gran, 0, p->gran_words * 8, hs));
-            p->epoch = 0;
-        }
         if (p->filt) {
             const rh_status pw = pre_launch(p, hs);
             if (pw != RH_OK) return pw;

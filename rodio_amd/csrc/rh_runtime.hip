@@ -1,5 +1,6 @@
 // rh_runtime.hip -- device bring-up, memory/stream/event helpers of the C ABI.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -21,9 +22,11 @@ void set_hip_error(hipError_t e, const char *what) {
 namespace {
 const char *const kKnobNames[K_COUNT] = {"RH_AGC_SEQ", "RH_AGC_VEC", "RH_BIQUAD_NO_FALLBACK", "RH_BIQUAD_SEQ", "RH_BIQUAD_R", "RH_BIQUAD_NW", "RH_BIQUAD_WGS", "RH_LIMIT_SEQ",
                                          "RH_LIMIT_R", "RH_LIMIT_NW", "RH_LIMIT_WGS", "RH_LIMIT_GRID", "RH_LIMIT_SKEW", "RH_LIMIT_NIO", "RH_LIMIT_INIT", "RH_SCAN_DMA_TOP", "RH_SCAN_SPIN_LIMIT", "RH_NO_HYBRID",
-                                         "RH_NO_TICKET_SHARDS", "RH_PROF_DUMP", "RH_HOST_ALLOC", "RH_NO_MIX_FIRST", "RH_MIX_U", "RH_NO_CHUNK", "RH_CHUNK_HALF", "RH_AUTOTUNE_LOG", "RH_RAG_RESIDENT", "RH_RAG_TWO_KERNELS", "RH_AGC_SEGMENTS", "RH_RS_PIPE", "RH_DASP_I64_VIA_F64", "RH_MIX_GROUPS", "RH_CLASSES_SIDE_BY_SIDE", "RH_AGC_FUSED_R4", "RH_STREAM_UPLOAD_ALWAYS", "RH_STREAM_NO_REJOIN", "RH_NO_SBLK", "RH_SBLK_KV", "RH_SBLK_NO_OVERLAP", "RH_CLASSES_ONE_BY_ONE", "RH_CLASSES_ONE_WAVE", "RH_WIDE_GENERAL", "RH_PCM_NO_TILE", "RH_PCM_TILE_KB", "RH_LERP_IEEE_DIV"};
+                                         "RH_NO_TICKET_SHARDS", "RH_PROF_DUMP", "RH_HOST_ALLOC", "RH_NO_MIX_FIRST", "RH_MIX_U", "RH_NO_CHUNK", "RH_CHUNK_HALF", "RH_AUTOTUNE_LOG", "RH_RAG_RESIDENT", "RH_RAG_TWO_KERNELS", "RH_AGC_SEGMENTS", "RH_RS_PIPE", "RH_DASP_I64_VIA_F64", "RH_MIX_GROUPS", "RH_CLASSES_SIDE_BY_SIDE", "RH_AGC_FUSED_R4", "RH_STREAM_UPLOAD_ALWAYS", "RH_STREAM_NO_REJOIN", "RH_NO_SBLK", "RH_SBLK_KV", "RH_SBLK_NO_OVERLAP", "RH_CLASSES_ONE_BY_ONE", "RH_CLASSES_ONE_WAVE", "RH_WIDE_GENERAL", "RH_PCM_NO_TILE", "RH_PCM_TILE_KB", "RH_LERP_IEEE_DIV", "RH_COUNTER_JUMP", "RH_STREAM_START"};
 std::string g_knob_val[K_COUNT];
 bool g_knob_set[K_COUNT];
+CounterJump g_jump{false, 0, 0, 0};
+std::atomic<uint32_t> g_scan_launches{0};
 }  // namespace
 void load_knobs() {
     for (int k = 0; k < K_COUNT; ++k) {
@@ -31,8 +34,14 @@ void load_knobs() {
         g_knob_set[k] = v != nullptr;
         g_knob_val[k] = v ? v : "";
     }
+    g_jump = CounterJump{false, 0, 0, 0};
+    g_scan_launches = 0;
+    unsigned a = 0, t = 0, l = 0;
+    if (g_knob_set[K_COUNTER_JUMP] && sscanf(g_knob_val[K_COUNTER_JUMP].c_str(), "%u:%u:%u", &a, &t, &l) == 3 && a >= 1) g_jump = CounterJump{true, a, t, l};
 }
 const char *knob(Knob k) { return g_knob_set[k] ? g_knob_val[k].c_str() : nullptr; }
+const CounterJump &counter_jump() { return g_jump; }
+bool scan_jump_due() { return g_jump.on && g_scan_launches.fetch_add(1) + 1 == g_jump.after; }
 namespace {
 // bytes [0, n) of p: the unaligned head and tail byte by byte, the 4-byte aligned body word by word
 __global__ void k_fill(unsigned char *p, uint32_t word, size_t n) {
@@ -43,6 +52,11 @@ __global__ void k_fill(unsigned char *p, uint32_t word, size_t n) {
     for (size_t i = i0; i < words; i += step) w[i] = word;
     if (i0 < head) p[i0] = (unsigned char)word;
     if (i0 < n - tail0) p[tail0 + i0] = (unsigned char)word;
+}
+__global__ void k_counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uint32_t d_shards) {
+    const uint32_t i = threadIdx.x;
+    if (i == 0) atomicAdd(ctl, d_ticket);
+    else if (i <= n_shards) atomicAdd(ctl + 32u * i, d_shards);
 }
 }  // namespace
 namespace {
@@ -130,6 +144,10 @@ static void drop_stream_scratch(hipStream_t s) {
     if (it == g_scratch.end()) return;
     if (it->second.p) (void)hipFree(it->second.p);
     g_scratch.erase(it);
+}
+hipError_t counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uint32_t d_shards, hipStream_t s) {
+    hipLaunchKernelGGL(k_counters_add, dim3(1), dim3(64), 0, s, ctl, d_ticket, n_shards < 63u ? n_shards : 63u, d_shards);
+    return hipGetLastError();
 }
 hipError_t fill_async(void *p, int value, size_t bytes, hipStream_t s) {
     if (!bytes) return hipSuccess;
