@@ -582,6 +582,34 @@ typedef struct rh_rlm_geometry_info {
 } rh_rlm_geometry_info;
 rh_status rh_rlm_geometry(rh_rlm *p, rh_rlm_geometry_info *info);
 
+/* ---- sources that start on the device: rodio's synthetic generators.  Nothing is pulled from the host or uploaded.
+ * SignalGenerator::new(rate, freq, Function) (src/source/signal_generator.rs:86-154) and SineWave / SquareWave /
+ * TriangleWave / SawtoothWave::new(freq) (sine.rs, square.rs, triangle.rs, sawtooth.rs: the same at DEFAULT_SAMPLE_RATE,
+ * 48 kHz).  A generator is its state, two floats: phase_step = 1 / (rate as f32 / freq) and the phase of the NEXT sample;
+ * and its function (RH_GEN_*).  init (host): the state of a new generator (phase 0); refuses freq <= 0 and NaN (the reference's assert!); +inf gives a NaN phase, as the reference's.  seek: try_seek,
+ * (as_secs_f32(pos) * rate as f32 / period).rem_euclid(1.0) (signal_generator.rs:148-153).  advance (host): the phase n
+ * samples on, bit for bit n steps of `(phase + phase_step).rem_euclid(1.0)` (signal_generator.rs:137), in far fewer steps.
+ * generate: row g of dst (dst + g * ld, ld >= n) receives the next n samples of generator g < n_gens (<= 65535), whose
+ * state is states_dev[2g .. 2g+1] and function functions_dev[g] (both DEVICE arrays); its phase moves on by n: the next
+ * call continues the stream.  Triangle, square and sawtooth are the reference's
+ * bits; sine is sinf of the reference's f32 argument.  A function code outside RH_GEN_* gives NaN samples.  dst
+ * must not alias the states or functions. */
+enum { RH_GEN_SINE = 0, RH_GEN_TRIANGLE = 1, RH_GEN_SQUARE = 2, RH_GEN_SAWTOOTH = 3 };
+rh_status rh_signal_generator_init(float state_host[2], uint32_t sample_rate, float frequency);
+rh_status rh_signal_generator_seek(float *phase_host, uint32_t sample_rate, float frequency, uint64_t pos_ns);
+float rh_signal_phase_advance(float phase, float phase_step, uint64_t n);
+rh_status rh_signal_generate(float *dst, uint64_t ld, uint64_t n, float *states_dev, const int32_t *functions_dev,
+                             uint32_t n_gens, rh_stream stream);
+/* chirp(rate, f0, f1, duration) (src/source/chirp.rs:11-97).  total_samples: (duration.as_secs_f64() * rate as f64) as u64
+ * (chirp.rs:36-44).  total_duration: Duration::from_secs_f64(total / rate) (chirp.rs:83-86), rounded to the nanosecond.
+ * rh_chirp: samples first .. first + n of the sweep (sample i: sin((i / rate) as f32 * TAU * freq_i), freq_i between f0 and f1
+ * by (i / total) as f32, chirp.rs:53-63); *out_n = what is left of it, at most n (the iterator ends at total).  Any
+ * u64 position: a seek is `first` (chirp.rs:88-96: min(pos * rate, total)). */
+rh_status rh_chirp_total_samples(uint32_t sample_rate, uint64_t duration_ns, uint64_t *total);
+rh_status rh_chirp_total_duration(uint32_t sample_rate, uint64_t total, uint64_t *secs, uint32_t *nanos);
+rh_status rh_chirp(float *dst, uint64_t first, uint64_t n, uint64_t total, uint32_t sample_rate, float start_frequency,
+                   float end_frequency, uint64_t *out_n, rh_stream stream);
+
 /* ---- multi-GPU: one process per GPU, sources sharded over the ranks, the mixer sum (src/mixer.rs:185-198 is the
  * only place rodio's streams meet) completed by ONE collective per mixed block over RCCL / xGMI.  Rank 0 calls
  * rh_comm_unique_id and hands the 128 bytes to the other ranks (any out-of-band channel); every rank then calls

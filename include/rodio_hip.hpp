@@ -27,6 +27,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <deque>
 #include <functional>
 #include <exception>
@@ -901,6 +902,8 @@ public:
         std::uint64_t blocks = 0;
         std::uint64_t d2h_samples = 0;     // samples of processed blocks copied to the host (0 for a source that keeps its blocks on the device)
         std::uint64_t device_samples = 0;  // samples handed to a consumer device-to-device (read_device)
+        std::uint64_t uploaded_samples = 0;   // upstream samples copied host-to-device into the chain's input
+        std::uint64_t generated_samples = 0;  // upstream samples a DeviceGenerator produced on the device (none of them crosses PCIe)
         double first_advance_s = 0;        // the advance that started the stream (prepare(), or the first next())
     };
     const Timing &timing() const { return timing_; }
@@ -1015,6 +1018,166 @@ private:
     bool primed_ = false, ended_ = false;
 };
 }  // namespace detail
+
+// ---------------------------------------------------------------- sources that start on the device ----
+/// A Source whose samples the library can produce in DEVICE memory (rh_generators.hip): rodio's synthetic generators.  A GpuSource
+/// whose upstream is one (and GpuMixer::add of one, bare or inside a chain) launches the generator into the chain's input buffer:
+/// nothing is pulled into host memory and nothing is uploaded (Timing::uploaded_samples stays 0, Timing::generated_samples counts).
+/// On the host, next() / read() compute the same stream (the sine's last bit may differ from the device's sinf).
+class DeviceGenerator : public Source {
+public:
+    /// The next n samples of the stream into DEVICE memory `ddst`, enqueued on `stream`; returns the count (less than n at the end).
+    virtual std::size_t fill_device(float *ddst, std::size_t n, rh_stream stream) = 0;
+    /// GpuSource's mode: read() only counts the samples it would hand out (the block's staging is not written), and fill_device()
+    /// produces those samples, in order, on the device.
+    void defer_reads(bool on) { defer_ = on; }
+    bool reads_deferred() const { return defer_; }
+
+protected:
+    bool defer_ = false;
+};
+
+/// signal_generator.rs:24-30
+enum class Function : std::int32_t { Sine = RH_GEN_SINE, Triangle = RH_GEN_TRIANGLE, Square = RH_GEN_SQUARE, Sawtooth = RH_GEN_SAWTOOTH };
+
+/// SignalGenerator::new(rate, frequency, Function) (signal_generator.rs:86-154): mono, endless, no spans, no total duration.
+/// frequency <= 0 or NaN throws (the reference's assert!); +inf gives a NaN phase, as the reference's.
+class SignalGenerator : public DeviceGenerator {
+public:
+    SignalGenerator(std::uint32_t sample_rate, float frequency, Function f) : rate_(sample_rate), freq_(frequency), fn_(f) {
+        float st[2];
+        check(rh_signal_generator_init(st, sample_rate, frequency), "SignalGenerator: frequency must be > 0 (signal_generator.rs:104)");
+        step_ = st[0];
+        phase_ = st[1];
+    }
+    std::optional<float> next() override {  // signal_generator.rs:134-139
+        const float v = value(phase_);
+        const float x = phase_ + step_;
+        phase_ = x - std::floor(x);  // rem_euclid(1.0) of a non-negative value (rh_generators.h)
+        return v;
+    }
+    std::size_t read(float *dst, std::size_t n) override {
+        if (defer_) return n;
+        return Source::read(dst, n);
+    }
+    std::uint16_t channels() const override { return 1; }
+    std::uint32_t sample_rate() const override { return rate_; }
+    std::optional<std::size_t> current_span_len() const override { return std::nullopt; }
+    std::optional<Nanos> total_duration() const override { return std::nullopt; }
+    SizeHint size_hint() const override { return SizeHint{SIZE_MAX, std::nullopt}; }  // signal_generator.rs:141-144
+    bool try_seek(Nanos pos) override {  // signal_generator.rs:148-153
+        float ph = 0.0f;
+        check(rh_signal_generator_seek(&ph, rate_, freq_, (std::uint64_t)pos.count()), "rh_signal_generator_seek");
+        phase_ = ph;
+        dev_dirty_ = true;
+        return true;
+    }
+    std::size_t fill_device(float *ddst, std::size_t n, rh_stream stream) override {
+        if (!n) return 0;
+        if (dev_dirty_) {  // the state (two floats and the function, not samples) goes up at the start and after a seek
+            dev_.reset(4);
+            float hs[4] = {step_, phase_, 0.0f, 0.0f};
+            const std::int32_t code = (std::int32_t)fn_;
+            std::memcpy(&hs[2], &code, sizeof code);
+            check(rh_memcpy_h2d(dev_.get(), hs, sizeof hs, stream), "rh_memcpy_h2d");
+            check(rh_stream_synchronize(stream), "rh_stream_synchronize");
+            dev_dirty_ = false;
+        }
+        check(rh_signal_generate(ddst, n, n, dev_.get(), reinterpret_cast<const std::int32_t *>(dev_.get() + 2), 1, stream), "rh_signal_generate");
+        if (!defer_) phase_ = rh_signal_phase_advance(phase_, step_, n);  // (the host's own stream goes on where the device's does)
+        return n;
+    }
+    float frequency() const { return freq_; }
+    Function function() const { return fn_; }
+    float phase() const { return phase_; }
+
+private:
+    float value(float p) const {  // signal_generator.rs:32-55; TAU = 6.2831855f32
+        switch (fn_) {
+            case Function::Sine: return std::sin(6.2831855f * p);
+            case Function::Triangle: return 4.0f * std::fabs(p - std::floor(p + 0.5f)) - 1.0f;
+            case Function::Square: return std::fmod(p, 1.0f) < 0.5f ? 1.0f : -1.0f;
+            default: return 2.0f * (p - std::floor(p + 0.5f));
+        }
+    }
+    std::uint32_t rate_;
+    float freq_;
+    Function fn_;
+    float step_ = 0.0f, phase_ = 0.0f;
+    detail::DeviceBuf dev_;
+    bool dev_dirty_ = true;
+};
+/// SineWave / SquareWave / TriangleWave / SawtoothWave::new(freq): the generator at DEFAULT_SAMPLE_RATE (sine.rs and its siblings).
+constexpr std::uint32_t kDefaultSampleRate = 48000;
+struct SineWave : SignalGenerator {
+    explicit SineWave(float frequency) : SignalGenerator(kDefaultSampleRate, frequency, Function::Sine) {}
+};
+struct SquareWave : SignalGenerator {
+    explicit SquareWave(float frequency) : SignalGenerator(kDefaultSampleRate, frequency, Function::Square) {}
+};
+struct TriangleWave : SignalGenerator {
+    explicit TriangleWave(float frequency) : SignalGenerator(kDefaultSampleRate, frequency, Function::Triangle) {}
+};
+struct SawtoothWave : SignalGenerator {
+    explicit SawtoothWave(float frequency) : SignalGenerator(kDefaultSampleRate, frequency, Function::Sawtooth) {}
+};
+
+/// chirp(rate, start_frequency, end_frequency, duration) (chirp.rs:11-97): mono, exact size_hint, ends at total_samples.
+class Chirp : public DeviceGenerator {
+public:
+    Chirp(std::uint32_t sample_rate, float start_frequency, float end_frequency, Nanos duration) : rate_(sample_rate), f0_(start_frequency), f1_(end_frequency) {
+        check(rh_chirp_total_samples(sample_rate, (std::uint64_t)duration.count(), &total_), "rh_chirp_total_samples");
+    }
+    std::optional<float> next() override {  // chirp.rs:50-64
+        if (i_ >= total_) return std::nullopt;
+        const float ratio = (float)((double)i_ / (double)total_);
+        const float freq = f0_ * (1.0f - ratio) + f1_ * ratio;
+        const float t = (float)((double)i_ / (double)rate_) * 6.2831855f * freq;
+        ++i_;
+        return std::sin(t);
+    }
+    std::size_t read(float *dst, std::size_t n) override {
+        if (!defer_) return Source::read(dst, n);
+        const std::uint64_t k = std::min<std::uint64_t>(n, total_ - pulled_);
+        pulled_ += k;
+        return (std::size_t)k;
+    }
+    std::uint16_t channels() const override { return 1; }
+    std::uint32_t sample_rate() const override { return rate_; }
+    std::optional<std::size_t> current_span_len() const override { return std::nullopt; }
+    SizeHint size_hint() const override {  // chirp.rs:66-69
+        const std::size_t r = (std::size_t)(total_ - (defer_ ? pulled_ : i_));
+        return SizeHint{r, r};
+    }
+    std::optional<Nanos> total_duration() const override {  // chirp.rs:83-86
+        std::uint64_t secs = 0;
+        std::uint32_t nanos = 0;
+        check(rh_chirp_total_duration(rate_, total_, &secs, &nanos), "rh_chirp_total_duration");
+        return Nanos((std::int64_t)(secs * 1000000000ull + nanos));
+    }
+    bool try_seek(Nanos pos) override {  // chirp.rs:88-96: min((pos.as_secs_f64() * rate) as u64, total)
+        std::uint64_t t = 0;
+        check(rh_chirp_total_samples(rate_, (std::uint64_t)pos.count(), &t), "rh_chirp_total_samples");
+        seek_sample(t);
+        return true;
+    }
+    /// The u64 sample position itself (positions past 2^32 are legal).
+    void seek_sample(std::uint64_t i) { i_ = pulled_ = std::min(i, total_); }
+    std::size_t fill_device(float *ddst, std::size_t n, rh_stream stream) override {
+        std::uint64_t m = 0;
+        check(rh_chirp(ddst, i_, n, total_, rate_, f0_, f1_, &m, stream), "rh_chirp");
+        i_ += m;
+        if (!defer_) pulled_ = i_;
+        return (std::size_t)m;
+    }
+    std::uint64_t total_samples() const { return total_; }
+    std::uint64_t elapsed_samples() const { return i_; }
+
+private:
+    std::uint32_t rate_;
+    float f0_, f1_;
+    std::uint64_t total_ = 0, i_ = 0, pulled_ = 0;  // i_: the next sample produced; pulled_: the next one read() hands out in deferred mode
+};
 
 // ---------------------------------------------------------------- parameters that change while a source plays ----
 /// What a periodic_access() closure reaches (rodio's `inner_mut()`): views onto the adjustable stages in front of the access point.
@@ -1201,6 +1364,7 @@ public:
         cur_in_ch_ = in_ch0_ = ch_;
         cur_in_rate_ = in_rate0_ = rate_;
         reader_ = detail::SpanReader(up_.get());
+        if ((gen_ = dynamic_cast<DeviceGenerator *>(up_.get()))) gen_->defer_reads(true);  // its samples are made on the device, where the chain reads them
     }
     ~GpuSource() override { (void)rh_stream_synchronize(stream_); }  // nothing of the chain may still run when its buffers go
     // -- Source.  The format is the one of the sample next() returns next: an upstream that changes its format between spans (a queue of
@@ -1244,7 +1408,10 @@ public:
     /// The last adapter of the chain is a `uniform` (what Mixer::add would wrap the chain in is already there).
     bool ends_with_uniform() const { return last_kind_ == 1; }
     Source &inner() { return *up_; }
-    BoxSource into_inner() { return std::move(up_); }
+    BoxSource into_inner() {
+        if (gen_) gen_->defer_reads(false), gen_ = nullptr;
+        return std::move(up_);
+    }
     /// The chain's stream can end inside a frame although its upstream keeps `Source`'s contract: reverb and delay count their
     /// silence in SAMPLES (delay.rs:14: every second stereo reverb ends inside a frame), and `uniform` over spans that cut frames hands
     /// on what rodio's converters make of the cut.  A consumer that works on whole frames (GpuMixer's fused streams) asks.
@@ -1983,7 +2150,13 @@ protected:
             pieces_.assign(all.begin() + (std::ptrdiff_t)run.p0, all.begin() + (std::ptrdiff_t)run.p1);
             float *cur = a_.get(), *oth = b_.get();
             std::size_t k = run.n;
-            if (k) check(rh_memcpy_h2d(cur, s.in.get() + run.off, k * sizeof(float), stream_), "rh_memcpy_h2d");
+            if (k && gen_) {  // (the pull above counted the samples; the generator makes them here, in the same order)
+                if (gen_->fill_device(cur, k, stream_) != k) throw Error(RH_ERR_INVALID, "GpuSource: the generator produced fewer samples than it handed out");
+                timing_.generated_samples += k;
+            } else if (k) {
+                check(rh_memcpy_h2d(cur, s.in.get() + run.off, k * sizeof(float), stream_), "rh_memcpy_h2d");
+                timing_.uploaded_samples += k;
+            }
             bool run_ends = flush && r + 1 == runs.size();  // the upstream ended, or a stage says so: the stages behind it see the end of their input
             for (Stage &st : stages_) {
                 Ctx c{oth, cur, k, cap, run_ends, stream_};
@@ -2487,6 +2660,7 @@ private:
     detail::SpanReader reader_{nullptr};
     std::vector<detail::Piece> pieces_;  // the spans of the block being enqueued
     bool span_aware_ = false;
+    DeviceGenerator *gen_ = nullptr;  // the upstream, when it makes its samples on the device
     int filter_mode_ = 0;  // 0: by the filter contract, per filter; 1: reference order throughout; 2: time-parallel throughout
     detail::DeviceBuf a_, b_;
     bool scan_kernels_ = false;  // the chain launches handle-less scan kernels: their failure word is read per block
@@ -2592,6 +2766,16 @@ public:
             if (!item.fusew) make_wide(item);
             if (joins_a_running_mix()) late_join(std::move(item));
             else pending_.push_back(std::move(item));
+            return;
+        }
+        // A generator (SignalGenerator, *Wave, Chirp) stays on the device: its own chain launches it, and the chain's blocks enter the mix
+        // device-to-device.  Mono into a stereo mix: the chain duplicates the channel first -- ChannelCountConverter(1 -> 2) commutes with the
+        // converter's per-channel interpolation, the amplify and the per-channel filter, so the samples are those of Mixer::add's
+        // UniformSourceIterator(src.amplify(g), 2, rate) (mixer.rs:58-66, uniform.rs:62-67).
+        if (dynamic_cast<DeviceGenerator *>(src.get()) && out_ch_ == 2 && ch <= 2) {
+            auto chain = std::make_unique<GpuSource>(std::move(src), opt_.block_frames);
+            if (ch == 1) chain->convert_channels(2);
+            add(std::move(chain), gain, filter);
             return;
         }
         // A source whose spans can end inside a frame (uniform.rs:56: 32768 is no multiple of 3, 5, 6, 7 channels) may end its converted
@@ -3388,6 +3572,7 @@ private:
         }
         g.wm = m_end;
         if (width) check(rh_memcpy_h2d_rows(din.get(), stage.get(), roww * sizeof(float), width * sizeof(float), S, copy_stream_), "rh_memcpy_h2d_rows");
+        timing_.uploaded_samples += (std::uint64_t)width * S;
         check(rh_event_record(g.copied[g.pslot].get(), copy_stream_), "rh_event_record");
     }
     /// ... and its device half: the one launch (per source Amplify -> SampleRateConverter -> ChannelCountConverter, and the ordered sum)
@@ -3558,6 +3743,7 @@ private:
             }
         // 3. one copy for all rows, on the copy stream: it runs beside the launches of the block before
         if (total) check(rh_memcpy_h2d(din.get(), stage.get(), total * sizeof(float), copy_stream_), "rh_memcpy_h2d");
+        timing_.uploaded_samples += total;
         check(rh_event_record(g.copied[g.pslot].get(), copy_stream_), "rh_event_record");
     }
     void issue_block_staged(Gen &g) {
@@ -3670,6 +3856,7 @@ private:
         for (std::size_t i = 0; i < S; ++i)
             if (g.srcs[i].ch == native) width = std::max<std::size_t>(width, (std::size_t)g.pavail[i] * native);
         if (width) check(rh_memcpy_h2d_rows(din.get(), stage.get(), row_ * sizeof(float), width * sizeof(float), S, copy_stream_), "rh_memcpy_h2d_rows");
+        timing_.uploaded_samples += (std::uint64_t)width * S;
         if (g.pside) check(rh_memcpy_h2d(dside.get(), side.get(), g.pside * sizeof(float), copy_stream_), "rh_memcpy_h2d");
         // chains that hand their blocks over on the device: [what the converter left of the block before | the chain's next samples],
         // device-to-device on the copy stream, behind the pitched copy (which also moved the rows' unused staging bytes)

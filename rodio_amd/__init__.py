@@ -11,6 +11,15 @@ from ._lib import LIB_PATH, RhError, lib
 from .source import (  # noqa: F401
     ChannelCountConverter,
     ChannelVolume,
+    Chirp,
+    GeneratorBank,
+    SawtoothWave,
+    SignalGenerator,
+    SineWave,
+    SquareWave,
+    TriangleWave,
+    chirp,
+    signal_phase_advance,
     GpuSource,
     Mixer,
     ResampleLowpassMix,

@@ -192,6 +192,13 @@ SIGNATURES = {
     "rh_rlm_geometry": (i32, [vp, C.POINTER(RlmGeometry)]),
     "rh_rlm_late_carries": (i32, [vp, C.POINTER(u64)]),
     "rh_rlm_phase_cycles": (i32, [vp, C.POINTER(C.c_double)]),
+    "rh_signal_generator_init": (i32, [f32p, u32, f32]),
+    "rh_signal_generator_seek": (i32, [f32p, u32, f32, u64]),
+    "rh_signal_phase_advance": (f32, [f32, f32, u64]),
+    "rh_signal_generate": (i32, [vp, u64, u64, vp, vp, u32, vp]),
+    "rh_chirp_total_samples": (i32, [u32, u64, C.POINTER(u64)]),
+    "rh_chirp_total_duration": (i32, [u32, u64, C.POINTER(u64), C.POINTER(u32)]),
+    "rh_chirp": (i32, [vp, u64, u64, u64, u32, f32, f32, C.POINTER(u64), vp]),
 }
 
 

@@ -888,3 +888,175 @@ def channel_volume_steps(x, in_ch: int, out_ch: int, first: int, gain_period: in
                                       int(factor_first), int(factor_period), _ptr(f) if f is not None else None, f.numel() if f is not None else 0,
                                       _stream()), "rh_channel_volume_steps")
     return out
+
+
+# ---- sources that start on the device: rodio's synthetic generators (rh_signal_generate / rh_chirp) -------------------------
+GEN_FUNCTIONS = {"sine": 0, "triangle": 1, "square": 2, "sawtooth": 3}  # rodio's Function (signal_generator.rs:24-30), RH_GEN_*
+DEFAULT_SAMPLE_RATE = 48000  # rodio::DEFAULT_SAMPLE_RATE
+USIZE_MAX = (1 << 64) - 1
+
+
+def _gen_function(f) -> int:
+    code = GEN_FUNCTIONS.get(f, f) if isinstance(f, str) else int(f)
+    if code not in GEN_FUNCTIONS.values():
+        raise ValueError(f"unknown generator function {f!r}: one of {sorted(GEN_FUNCTIONS)}")
+    return code
+
+
+def _gen_state(sample_rate, frequency):
+    st = (C.c_float * 2)()
+    check(lib.rh_signal_generator_init(st, int(sample_rate), float(frequency)), "rh_signal_generator_init (frequency must be > 0)")
+    return st[0], st[1]
+
+
+class GeneratorBank:
+    """G SignalGenerators whose state (phase_step, phase) lives in device memory.  take(n) fills a [G, n] device tensor, row g
+    with generator g's next n samples, and moves every phase on: the next take continues the streams.  Nothing is uploaded."""
+
+    def __init__(self, sample_rates, frequencies, functions):
+        torch = _t()
+        _ensure()
+        g = len(frequencies)
+        rates = [int(r) for r in (sample_rates if hasattr(sample_rates, "__len__") else [sample_rates] * g)]
+        fns = [_gen_function(f) for f in (functions if isinstance(functions, (list, tuple)) else [functions] * g)]
+        if not (len(rates) == len(fns) == g) or g == 0:
+            raise ValueError("one sample rate, frequency and function per generator")
+        self.rates, self.freqs, self.functions = rates, [float(np.float32(f)) for f in frequencies], fns
+        st = [_gen_state(r, f) for r, f in zip(rates, self.freqs)]
+        self.state = torch.tensor(np.asarray(st, np.float32).reshape(-1), device="cuda")
+        self._fns = torch.tensor(fns, dtype=torch.int32, device="cuda")
+
+    def __len__(self):
+        return len(self.freqs)
+
+    def take(self, n: int, out=None):
+        torch = _t()
+        g = len(self)
+        if out is None:
+            out = torch.empty((g, int(n)), dtype=torch.float32, device="cuda")
+        if out.dim() != 2 or out.shape[0] != g or out.shape[1] < n or out.stride(1) != 1:
+            raise ValueError("out must be [G, >= n] with contiguous rows")
+        check(lib.rh_signal_generate(_ptr(out), out.stride(0), int(n), _ptr(self.state), _ptr(self._fns), g, _stream()), "rh_signal_generate")
+        return out[:, : int(n)]
+
+    def phases(self) -> np.ndarray:
+        return self.state.view(-1, 2)[:, 1].cpu().numpy()
+
+    def try_seek(self, pos_ns: int):
+        """Every generator's try_seek(pos) (signal_generator.rs:148-153)."""
+        ph = (C.c_float * 1)()
+        new = np.empty(len(self), np.float32)
+        for k, (r, f) in enumerate(zip(self.rates, self.freqs)):
+            check(lib.rh_signal_generator_seek(ph, r, f, int(pos_ns)), "rh_signal_generator_seek")
+            new[k] = ph[0]
+        self.state.view(-1, 2)[:, 1].copy_(_t().from_numpy(new).cuda())
+
+
+class SignalGenerator:
+    """rodio's SignalGenerator::new(sample_rate, frequency, Function) on the device: take(n) returns its next n samples as a
+    device tensor (source(n): as a mono GpuSource).  Mono, endless: size_hint (usize::MAX, None), no span length, no total
+    duration.  frequency <= 0 or NaN raises RhError (rodio panics)."""
+
+    def __init__(self, sample_rate: int, frequency: float, function="sine"):
+        self._bank = GeneratorBank([sample_rate], [frequency], [function])
+
+    def channels(self) -> int:
+        return 1
+
+    def sample_rate(self) -> int:
+        return self._bank.rates[0]
+
+    def current_span_len(self):
+        return None
+
+    def total_duration(self):
+        return None
+
+    def size_hint(self):
+        return (USIZE_MAX, None)
+
+    def phase(self) -> float:
+        return float(self._bank.phases()[0])
+
+    def take(self, n: int):
+        return self._bank.take(n)[0]
+
+    def source(self, n: int) -> GpuSource:
+        return GpuSource(self.take(n), 1, self.sample_rate())
+
+    def try_seek(self, pos_ns: int):
+        self._bank.try_seek(pos_ns)
+
+
+def SineWave(frequency: float) -> SignalGenerator:  # sine.rs: SignalGenerator at DEFAULT_SAMPLE_RATE
+    return SignalGenerator(DEFAULT_SAMPLE_RATE, frequency, "sine")
+
+
+def SquareWave(frequency: float) -> SignalGenerator:
+    return SignalGenerator(DEFAULT_SAMPLE_RATE, frequency, "square")
+
+
+def TriangleWave(frequency: float) -> SignalGenerator:
+    return SignalGenerator(DEFAULT_SAMPLE_RATE, frequency, "triangle")
+
+
+def SawtoothWave(frequency: float) -> SignalGenerator:
+    return SignalGenerator(DEFAULT_SAMPLE_RATE, frequency, "sawtooth")
+
+
+def signal_phase_advance(phase: float, phase_step: float, n: int) -> float:
+    """rh_signal_phase_advance (host): the phase n samples on, bit for bit n steps of rodio's recurrence."""
+    return float(np.float32(lib.rh_signal_phase_advance(float(phase), float(phase_step), int(n))))
+
+
+class Chirp:
+    """rodio's chirp(sample_rate, start_frequency, end_frequency, duration) on the device (chirp.rs).  take(n) returns the next
+    min(n, remaining) samples; try_seek takes any u64 sample position."""
+
+    def __init__(self, sample_rate: int, start_frequency: float, end_frequency: float, duration_ns: int):
+        _ensure()
+        t = C.c_uint64(0)
+        check(lib.rh_chirp_total_samples(int(sample_rate), int(duration_ns), C.byref(t)), "rh_chirp_total_samples")
+        self._rate, self.f0, self.f1 = int(sample_rate), float(np.float32(start_frequency)), float(np.float32(end_frequency))
+        self.total_samples, self.elapsed_samples = t.value, 0
+
+    def channels(self) -> int:
+        return 1
+
+    def sample_rate(self) -> int:
+        return self._rate
+
+    def current_span_len(self):
+        return None
+
+    def size_hint(self):
+        r = self.total_samples - self.elapsed_samples
+        return (r, r)
+
+    def total_duration(self) -> int:
+        """Duration::from_secs_f64(total / rate), in nanoseconds."""
+        s, ns = C.c_uint64(0), C.c_uint32(0)
+        check(lib.rh_chirp_total_duration(self._rate, self.total_samples, C.byref(s), C.byref(ns)), "rh_chirp_total_duration")
+        return s.value * 1_000_000_000 + ns.value
+
+    def try_seek(self, pos_ns: int):
+        t = C.c_uint64(0)  # (pos.as_secs_f64() * rate as f64) as u64: the same formula as the total
+        check(lib.rh_chirp_total_samples(self._rate, int(pos_ns), C.byref(t)), "rh_chirp_total_samples")
+        self.elapsed_samples = min(t.value, self.total_samples)
+
+    def seek_sample(self, i: int):
+        self.elapsed_samples = min(int(i), self.total_samples)
+
+    def take(self, n: int):
+        out = _dev_empty(max(int(n), 1))
+        m = C.c_uint64(0)
+        check(lib.rh_chirp(_ptr(out), self.elapsed_samples, int(n), self.total_samples, self._rate, self.f0, self.f1, C.byref(m), _stream()), "rh_chirp")
+        self.elapsed_samples += m.value
+        return out[: m.value]
+
+    def source(self, n: int) -> GpuSource:
+        return GpuSource(self.take(n), 1, self._rate)
+
+
+def chirp(sample_rate: int, start_frequency: float, end_frequency: float, duration_ns: int) -> Chirp:
+    return Chirp(sample_rate, start_frequency, end_frequency, duration_ns)

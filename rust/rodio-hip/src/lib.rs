@@ -2175,3 +2175,163 @@ impl Drop for GpuMixer {
         unsafe { rh_stream_destroy(self.copy_stream); }
     }
 }
+
+// ------------------------------------------------------------------------------------------------ generators ----
+/// rodio's `Function` (`signal_generator.rs:24-30`), numbered as `RH_GEN_*`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Function { Sine = 0, Triangle = 1, Square = 2, Sawtooth = 3 }
+
+/// A source whose samples the library makes in DEVICE memory (`rh_generators.hip`): the twin of `rodio_hip::DeviceGenerator`.
+pub trait DeviceGenerator: Source {
+    /// The next `n` samples of the stream into device memory `ddst`, enqueued on `stream`; the count (less than `n` at the end).
+    fn fill_device(&mut self, ddst: *mut f32, n: usize, stream: RhStream) -> usize;
+}
+
+/// `SignalGenerator::new(rate, frequency, Function)` (`signal_generator.rs:86-154`) on the device: mono, endless, no spans, no total
+/// duration.  `next()` serves blocks the device made (`rh_signal_generate`) from page-locked memory; `fill_device` writes into a
+/// consumer's device buffer.  `frequency <= 0` or NaN panics, as rodio's `assert!`.
+pub struct GpuSignalGenerator { rate: u32, freq: f32, function: Function, state: [f32; 2], dev: DeviceBuf, dirty: bool, stream: RhStream,
+                                 block: PinnedBuf, dblock: DeviceBuf, pos: usize, len: usize }
+unsafe impl Send for GpuSignalGenerator {}
+impl GpuSignalGenerator {
+    const BLOCK: usize = 1 << 15;
+    pub fn new(sample_rate: SampleRate, frequency: f32, function: Function) -> Self {
+        let mut state = [0.0f32; 2];
+        ck(unsafe { rh_signal_generator_init(state.as_mut_ptr(), sample_rate.get(), frequency) }, "SignalGenerator: frequency must be > 0");
+        let mut stream: RhStream = ptr::null_mut();
+        ck(unsafe { rh_stream_create(&mut stream) }, "rh_stream_create");
+        GpuSignalGenerator { rate: sample_rate.get(), freq: frequency, function, state, dev: DeviceBuf::new(), dirty: true, stream,
+                             block: PinnedBuf::new(), dblock: DeviceBuf::new(), pos: 0, len: 0 }
+    }
+    /// `SineWave::new(freq)` and its siblings: the generator at `DEFAULT_SAMPLE_RATE` (`sine.rs`, `square.rs`, `triangle.rs`, `sawtooth.rs`).
+    pub fn sine_wave(freq: f32) -> Self { Self::new(rodio::DEFAULT_SAMPLE_RATE, freq, Function::Sine) }
+    pub fn square_wave(freq: f32) -> Self { Self::new(rodio::DEFAULT_SAMPLE_RATE, freq, Function::Square) }
+    pub fn triangle_wave(freq: f32) -> Self { Self::new(rodio::DEFAULT_SAMPLE_RATE, freq, Function::Triangle) }
+    pub fn sawtooth_wave(freq: f32) -> Self { Self::new(rodio::DEFAULT_SAMPLE_RATE, freq, Function::Sawtooth) }
+    fn upload_state(&mut self, stream: RhStream) {
+        if !self.dirty { return; }
+        self.dev.reserve(4);
+        let code = self.function as i32;
+        let hs: [f32; 4] = [self.state[0], self.state[1], f32::from_bits(code as u32), 0.0];
+        unsafe {
+            ck(rh_memcpy_h2d(self.dev.p.cast(), hs.as_ptr().cast(), 16, stream), "rh_memcpy_h2d");
+            ck(rh_stream_synchronize(stream), "rh_stream_synchronize");
+        }
+        self.dirty = false;
+    }
+}
+impl DeviceGenerator for GpuSignalGenerator {
+    fn fill_device(&mut self, ddst: *mut f32, n: usize, stream: RhStream) -> usize {
+        if n == 0 { return 0; }
+        self.upload_state(stream);
+        unsafe {
+            ck(rh_signal_generate(ddst, n as u64, n as u64, self.dev.p, self.dev.p.add(2) as *const i32, 1, stream), "rh_signal_generate");
+            self.state[1] = rh_signal_phase_advance(self.state[1], self.state[0], n as u64);  // the host's copy of the phase goes on with the device's
+        }
+        n
+    }
+}
+impl Iterator for GpuSignalGenerator {
+    type Item = f32;
+    fn next(&mut self) -> Option<f32> {
+        if self.pos == self.len {
+            let n = Self::BLOCK;
+            self.block.reserve(n);
+            self.dblock.reserve(n);
+            let (d, s) = (self.dblock.p, self.stream);
+            self.fill_device(d, n, s);
+            unsafe {
+                ck(rh_memcpy_d2h(self.block.p.cast(), d.cast(), n * 4, s), "rh_memcpy_d2h");
+                ck(rh_stream_synchronize(s), "rh_stream_synchronize");
+            }
+            self.pos = 0;
+            self.len = n;
+        }
+        let v = unsafe { *self.block.p.add(self.pos) };
+        self.pos += 1;
+        Some(v)
+    }
+    fn size_hint(&self) -> (usize, Option<usize>) { (usize::MAX, None) }  // signal_generator.rs:141-144
+}
+impl Source for GpuSignalGenerator {
+    fn current_span_len(&self) -> Option<usize> { None }
+    fn channels(&self) -> ChannelCount { ChannelCount::new(1).unwrap() }
+    fn sample_rate(&self) -> SampleRate { SampleRate::new(self.rate).unwrap() }
+    fn total_duration(&self) -> Option<Duration> { None }
+    fn try_seek(&mut self, pos: Duration) -> Result<(), SeekError> {  // signal_generator.rs:148-153
+        let mut ph = 0.0f32;
+        ck(unsafe { rh_signal_generator_seek(&mut ph, self.rate, self.freq, pos.as_nanos().min(u64::MAX as u128) as u64) }, "rh_signal_generator_seek");
+        self.state[1] = ph;
+        self.dirty = true;
+        self.pos = 0;
+        self.len = 0;  // what was made ahead is dropped
+        Ok(())
+    }
+}
+impl Drop for GpuSignalGenerator { fn drop(&mut self) { unsafe { rh_stream_synchronize(self.stream); rh_stream_destroy(self.stream); } } }
+
+/// `chirp(rate, start_frequency, end_frequency, duration)` (`chirp.rs:11-97`) on the device (`rh_chirp`): exact size hint, any u64
+/// position.
+pub struct GpuChirp { rate: u32, f0: f32, f1: f32, total: u64, i: u64, stream: RhStream, block: PinnedBuf, dblock: DeviceBuf, pos: usize, len: usize }
+unsafe impl Send for GpuChirp {}
+impl GpuChirp {
+    const BLOCK: usize = 1 << 15;
+    pub fn new(sample_rate: SampleRate, start_frequency: f32, end_frequency: f32, duration: Duration) -> Self {
+        let mut total = 0u64;
+        ck(unsafe { rh_chirp_total_samples(sample_rate.get(), duration.as_nanos().min(u64::MAX as u128) as u64, &mut total) }, "rh_chirp_total_samples");
+        let mut stream: RhStream = ptr::null_mut();
+        ck(unsafe { rh_stream_create(&mut stream) }, "rh_stream_create");
+        GpuChirp { rate: sample_rate.get(), f0: start_frequency, f1: end_frequency, total, i: 0, stream, block: PinnedBuf::new(), dblock: DeviceBuf::new(), pos: 0, len: 0 }
+    }
+    /// The u64 sample position itself (chirp.rs:88-96 clamps it to the total).
+    pub fn seek_sample(&mut self, i: u64) { self.i = i.min(self.total); self.pos = 0; self.len = 0; }
+    fn remaining(&self) -> u64 { self.total - self.i + (self.len - self.pos) as u64 }
+}
+impl DeviceGenerator for GpuChirp {
+    fn fill_device(&mut self, ddst: *mut f32, n: usize, stream: RhStream) -> usize {
+        let mut m = 0u64;
+        ck(unsafe { rh_chirp(ddst, self.i, n as u64, self.total, self.rate, self.f0, self.f1, &mut m, stream) }, "rh_chirp");
+        self.i += m;
+        m as usize
+    }
+}
+impl Iterator for GpuChirp {
+    type Item = f32;
+    fn next(&mut self) -> Option<f32> {
+        if self.pos == self.len {
+            self.block.reserve(Self::BLOCK);
+            self.dblock.reserve(Self::BLOCK);
+            let (d, s) = (self.dblock.p, self.stream);
+            let m = self.fill_device(d, Self::BLOCK, s);
+            if m == 0 { return None; }
+            unsafe {
+                ck(rh_memcpy_d2h(self.block.p.cast(), d.cast(), m * 4, s), "rh_memcpy_d2h");
+                ck(rh_stream_synchronize(s), "rh_stream_synchronize");
+            }
+            self.pos = 0;
+            self.len = m;
+        }
+        let v = unsafe { *self.block.p.add(self.pos) };
+        self.pos += 1;
+        Some(v)
+    }
+    fn size_hint(&self) -> (usize, Option<usize>) { let r = self.remaining() as usize; (r, Some(r)) }  // chirp.rs:66-69
+}
+impl ExactSizeIterator for GpuChirp {}
+impl Source for GpuChirp {
+    fn current_span_len(&self) -> Option<usize> { None }
+    fn channels(&self) -> ChannelCount { ChannelCount::new(1).unwrap() }
+    fn sample_rate(&self) -> SampleRate { SampleRate::new(self.rate).unwrap() }
+    fn total_duration(&self) -> Option<Duration> {  // chirp.rs:83-86
+        let (mut secs, mut nanos) = (0u64, 0u32);
+        ck(unsafe { rh_chirp_total_duration(self.rate, self.total, &mut secs, &mut nanos) }, "rh_chirp_total_duration");
+        Some(Duration::new(secs, nanos))
+    }
+    fn try_seek(&mut self, pos: Duration) -> Result<(), SeekError> {
+        let mut t = 0u64;  // (pos.as_secs_f64() * rate as f64) as u64: the formula of the total
+        ck(unsafe { rh_chirp_total_samples(self.rate, pos.as_nanos().min(u64::MAX as u128) as u64, &mut t) }, "rh_chirp_total_samples");
+        self.seek_sample(t);
+        Ok(())
+    }
+}
+impl Drop for GpuChirp { fn drop(&mut self) { unsafe { rh_stream_synchronize(self.stream); rh_stream_destroy(self.stream); } } }
