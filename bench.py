@@ -3,15 +3,22 @@
 
     python bench.py --gpus N --steps K --warmup W          # 256 sources/GPU x 1 Mi stereo frames, 44.1 -> 48 kHz
                                                            # linear resample + low_pass(200) + ordered Mixer sum
+    python bench.py --gpus N --steps K --warmup W --full   # the same line, plus every check and side measurement below
 
 A "step" is one pass of the fused hot path (rh_rlm_run) over one batch of S x N input frames already resident in
 HBM, plus -- for N > 1 ranks -- the RCCL all-reduce of the mixed block (sources are sharded S per rank: weak scaling;
 SURVEY.md 8(e)).  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: it makes the inputs, autotunes the launch geometry, warms up, times the
+steps, writes --dump-outputs and prints `value`, `ms_per_step` and `roofline` (the kernel's HIP-event time; `traffic` null).
+`--full` adds what takes runs of its own: `cpu_baseline`, `parity` (with `unscaled` / `vs_f64`), the counter passes behind
+`roofline.traffic`, `roofline.per_source`, `roofline.per_class`, `roofline.side` and, for N > 1, `multi_gpu`.  The timed steps
+and what they compute are the same either way.
+
   value        = interleaved INPUT samples consumed per second over all ranks, in Msamples/s (S*N*C / t).
   roofline     = algorithmic bytes of one launch (4*S*N*C read + 4*M*C written) / the kernel's mean duration, measured with
-                 HIP events on the launch stream inside the timed region, against the 8 TB/s HBM3E peak.  `traffic` = HBM bytes
-                 per launch from the TCC counters, collected live by two `rocprofv3 --pmc` passes of this script (FETCH_SIZE,
+                 HIP events on the launch stream inside the timed region, against the 8 TB/s HBM3E peak.  `traffic` (--full) = HBM
+                 bytes per launch from the TCC counters, collected live by two `rocprofv3 --pmc` passes of this script (FETCH_SIZE,
                  WRITE_SIZE; FETCH_SIZE x 2 on gfx950, MI355X_MICROARCH.md "HBM") unless RH_BENCH_NO_PMC=1.
   cpu_baseline = the restated rodio CPU iterator path (oracle/, "port": the reference is Rust and cannot be compiled here), one
                  thread, on the WHOLE workload (12-13 s); `all_cores` = the same with the sources sharded over the host's cores
@@ -22,13 +29,15 @@ SURVEY.md 8(e)).  Rank 0 prints ONE JSON line.
                  traffic and parity of the GENERAL kernel beside the headline's specialisation.
 
 N > 1: `python bench.py --gpus N` starts its own N ranks (torch.distributed.run on 127.0.0.1) when no launcher has; under the
-driver's `python -m torch.distributed.run ... bench.py --gpus N` it is a rank.  The line then also carries `multi_gpu` (ranks
+driver's `python -m torch.distributed.run ... bench.py --gpus N` it is a rank.  With --full the line then also carries `multi_gpu` (ranks
 seen, the collective alone through torch.distributed AND through the C ABI's rh_allreduce_sum_f32, overlap, the reduced block
 against the ranks' partials), `parity` of the ALL-REDUCED block against the oracle over all S*N sources (every rank runs the
 oracle over its shard on its share of the cores), `cpu_baseline` and rank 0's `roofline` with live traffic.  The kernel's tiles go
 by ticket there (rh_rlm_set_exclusive(0)): RCCL's kernels share the CUs.
 
-The other configurations (single GPU, one JSON line each; evidence for the numbers in DESIGN.md / README.md):
+The other configurations (single GPU, one JSON line each; evidence for the numbers in DESIGN.md / README.md).  2span, 2mono and
+ragged are the headline's line on another workload and take --full as it does; the others are asked for by name and always
+carry their `parity`, `cpu_baseline` and counter `traffic`:
 
     python bench.py --config 2span      # config 2 with current_span_len = 32768 (uniform.rs:56-67 restarts the converter)
     python bench.py --config 2mono      # config 2 on MONO sources (the fused kernels' channel count is a template parameter)
@@ -94,12 +103,19 @@ def dump_outputs(d, arrays):
 
 def make_sources(S, N, first, total, ch=2):
     """[S, N*ch] f32 on the host: source `first + s` of a `total`-source job, U(-1,1) / total from
-    numpy.random.default_rng(1234 + global index) -- BASELINE.md section 3, cfg 2 and cfg 4."""
+    numpy.random.default_rng(1234 + global index) -- BASELINE.md section 3, cfg 2 and cfg 4.  Every row has a generator of its own,
+    so the rows are made on a few host threads (numpy drops the GIL while it fills) and come out the same as one after the other."""
+    from concurrent.futures import ThreadPoolExecutor
+
     import numpy as np
 
     x = np.empty((S, N * ch), dtype=np.float32)
-    for s in range(S):
+
+    def row(s):
         x[s] = (np.random.default_rng(1234 + first + s).uniform(-1.0, 1.0, ch * N) * (1.0 / total)).astype(np.float32)
+
+    with ThreadPoolExecutor(max(1, min(16, S, len(os.sched_getaffinity(0))))) as ex:
+        list(ex.map(row, range(S)))
     return x
 
 
@@ -362,6 +378,7 @@ def headline(args, argv):
     span = 32768 if args.config == "2span" else args.span
     ragged = args.config == "ragged"
     child = os.environ.get("RH_BENCH_CHILD") == "1"  # a rocprofv3 --pmc pass of ourselves: same launches, no extras
+    full = args.full  # the legs after the timed steps (module docstring); a plain run writes --dump-outputs and the line alone
     # sources [rank*S, (rank+1)*S) of a (S*world)-source job: seeds 1234 + global index, scale 1/(S*world) (cfg 2 / cfg 4)
     host = make_sources(S, N, rank * S, S * world, Cn)
     data = torch.from_numpy(host).cuda()
@@ -457,7 +474,7 @@ def headline(args, argv):
     # ---- untimed diagnostics of the N > 1 path: the collective alone, the reduced block against the ranks' partials, the ranks seen --
     multi = None
     local = None
-    if world > 1:
+    if world > 1 and full:
         kmax = allreduce_scalar(kernel_avg_ms, dist.ReduceOp.MAX)
         kmin = allreduce_scalar(kernel_avg_ms, dist.ReduceOp.MIN)
         seen = int(round(allreduce_scalar(1.0, dist.ReduceOp.SUM)))
@@ -518,7 +535,7 @@ def headline(args, argv):
     # ---- the per-source path in the same run: the same batch with every source on its own through the converter and the filter
     # (rh_rlm_set_mix_first(0): what sources with filters / lengths of their own take) -- the general number beside the headline's
     per_source = None
-    if not ragged and not args.per_source and not args.no_per_source and pipe.geometry().get("mix_first"):
+    if full and not ragged and not args.per_source and not args.no_per_source and pipe.geometry().get("mix_first"):
         pipe.set_mix_first(False)
         pipe.set_sources([data[s, : Cn * lens[s]] for s in range(S)])
         if not (args.no_autotune or args.frames_per_lane or args.ring_stages):
@@ -544,7 +561,7 @@ def headline(args, argv):
     # sources dealt over four filters, 64 each (rh_rlm_set_filters: one mix-first launch per class, the classes' mixes added in order of first
     # appearance); parity against the oracle's Mixer over the per-source chains, the classes' oracle mixes computed on four host threads
     per_class = None
-    if not ragged and not args.per_source and not args.no_per_class and world == 1 and Cn == 2 and not span and S % 4 == 0 and not child:
+    if full and not ragged and not args.per_source and not args.no_per_class and world == 1 and Cn == 2 and not span and S % 4 == 0 and not child:
         classes = [("low_pass", args.freq), ("low_pass", 1000), ("high_pass", 1000), ("low_pass", 4000)]
         pc = rh.ResampleLowpassMix(44100, 48000, Cn, None, "low_pass", args.freq, 0.5, max_sources=S, max_in_frames=N)
         pc.set_filters([classes[s_ % 4] for s_ in range(S)])
@@ -595,7 +612,8 @@ def headline(args, argv):
     cores = os.cpu_count() or 1
     base = parity = None
     ref = None
-    if not args.no_cpu_baseline and ragged and world == 1:  # sources of different lengths: the oracle's Mixer over per-source chains, one thread, the whole workload
+    with_oracle = full and not args.no_cpu_baseline
+    if with_oracle and ragged and world == 1:  # sources of different lengths: the oracle's Mixer over per-source chains, one thread, the whole workload
         from oracle import rodio_oracle as O
 
         t0 = time.perf_counter()
@@ -610,7 +628,7 @@ def headline(args, argv):
         d = np.abs(got.astype(np.float64) - ref.astype(np.float64)) if got.shape == ref.shape else None
         parity = ({"frames_compared": int(len(ref) // Cn), "of": int(M), "max_abs_err": float(d.max()), "peak": float(np.abs(ref).max()), "tolerance": 1e-5, "ok": bool(d.max() <= 1e-5),
                    "vs": "oracle Mixer over the per-source chains, the timed launch's whole block"} if d is not None else {"ok": False, "error": f"length {got.shape} vs oracle {ref.shape}"})
-    elif not args.no_cpu_baseline and not ragged and world == 1:
+    elif with_oracle and not ragged and world == 1:
         base, ref = cpu_baseline(host, S, N, span, args.freq, ch=Cn)
         got = mixed_last.cpu().numpy()  # the last timed launch's block
         if got.shape == ref.shape:
@@ -653,7 +671,7 @@ def headline(args, argv):
                     parity["unscaled"] = {"ok": False, "error": f"lengths {got_u.shape} / {ref_u.shape} / {t64.shape}"}
         else:
             parity = {"ok": False, "error": f"length {got.shape} vs oracle {ref.shape}"}
-    elif not args.no_cpu_baseline and not ragged:
+    elif with_oracle and not ragged:
         # N > 1.  (1) rank 0 times the one-thread oracle on a bounded sample of ITS shard while the other ranks wait (no contention
         # for the cores); (2) every rank runs the oracle over its whole shard on its share of the cores; (3) its own partial mix is
         # compared with that, and the ALL-REDUCED block of the last timed step with the f64 sum of all ranks' oracle mixes.
@@ -693,7 +711,7 @@ def headline(args, argv):
         ps = {"kernel": "k_rlm_fast (every source through the converter and the filter on its own, merged filter state)", "kernel_ms": per_source["kernel_ms"],
               "achieved": alg_b / (per_source["kernel_ms"] * 1e-3) / 1e9, "frac": alg_b / (per_source["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "geometry": per_source["geometry"]}
         cmp_ref = ref if world == 1 else None
-        if world > 1 and not args.no_cpu_baseline:
+        if world > 1 and with_oracle:
             cmp_ref = ref_shard
         if cmp_ref is not None:
             gotp = per_source["out"].cpu().numpy().astype(np.float64)
@@ -717,15 +735,17 @@ def headline(args, argv):
     alg_bytes = 4 * in_samples + 4 * M * Cn
     achieved = alg_bytes / (kernel_avg_ms * 1e-3) / 1e9 if kernel_avg_ms > 0 else 0.0
     geo = pipe.geometry()
-    # the profiling passes repeat this run's launches: same workload, the geometry the autotune kept, no autotune of their own
-    child_argv = [a for a in argv]
-    child_argv[child_argv.index("--frames-per-lane") + 1] = str(geo["frames_per_lane"])
-    child_argv[child_argv.index("--ring-stages") + 1] = str(geo["ring_stages"])
-    if world > 1 or args.shared_device or want.startswith("native"):
-        child_argv.append("--shared-device")  # tiles by ticket, as in this run
-    # (a ragged batch and a mix-first batch are two kernels per launch: the sum over both, per call)
-    two = bool(geo["ragged_pair"]) or geo.get("mix_first") == 1
-    traffic, traffic_how = pmc_traffic(child_argv, ["%k_rlm%", "%k_mix_%"], per_call=two)
+    traffic, traffic_how = None, "not measured in a plain run (--full runs the counter passes)"
+    if full:
+        # the profiling passes repeat this run's launches: same workload, the geometry the autotune kept, no autotune of their own
+        child_argv = [a for a in argv]
+        child_argv[child_argv.index("--frames-per-lane") + 1] = str(geo["frames_per_lane"])
+        child_argv[child_argv.index("--ring-stages") + 1] = str(geo["ring_stages"])
+        if world > 1 or args.shared_device or want.startswith("native"):
+            child_argv.append("--shared-device")  # tiles by ticket, as in this run
+        # (a ragged batch and a mix-first batch are two kernels per launch: the sum over both, per call)
+        two = bool(geo["ragged_pair"]) or geo.get("mix_first") == 1
+        traffic, traffic_how = pmc_traffic(child_argv, ["%k_rlm%", "%k_mix_%"], per_call=two)
     if per_source is not None:
         pa = [a for a in argv]
         pa[pa.index("--frames-per-lane") + 1] = str(per_source["geometry"]["frames_per_lane"])
@@ -744,7 +764,7 @@ def headline(args, argv):
     # time per call, fraction of the 8 TB/s roofline and parity; bounded (a few seconds each; python bench.py --config {3,5,stream} are the
     # full lines with cpu_baseline and counter traffic).
     side_legs = None
-    if world == 1 and args.config == "2" and not child and not args.per_source and not args.no_side and not ragged:
+    if full and world == 1 and args.config == "2" and not child and not args.per_source and not args.no_side and not ragged:
         import copy
 
         side_legs = {}
@@ -1201,17 +1221,20 @@ def main():
     ap.add_argument("--no-balance", type=int, default=0)
     ap.add_argument("--force-general", type=int, default=0)
     ap.add_argument("--no-autotune", action="store_true", help="keep the cost model's launch geometry")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--per-source", action="store_true", help="the headline batch on the per-source path (rh_rlm_set_mix_first(0)); the default line carries it as roofline.per_source")
-    ap.add_argument("--no-per-source", action="store_true", help="skip the per-source leg of the default line")
-    ap.add_argument("--no-per-class", action="store_true", help="skip roofline.per_class (the same sources with a filter per source: four classes of 64)")
-    ap.add_argument("--no-side", action="store_true", help="skip roofline.side (configs 3, 5 and the block-streamed headline workload in the default line)")
-    ap.add_argument("--no-unscaled", action="store_true", help="skip parity.unscaled / parity.vs_f64 (the same workload at amplitude 1, and both sides against the f64 response)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the CPU baseline, the parity checks, the counter passes, the per-source, per-class and side legs "
+                         "and (N > 1) multi_gpu; a plain run prints the headline figure alone (the --config 3/5/limit/agc/biquad/stream lines always carry their checks)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline and parity (side configs: without them at all)")
+    ap.add_argument("--per-source", action="store_true", help="the headline batch on the per-source path (rh_rlm_set_mix_first(0)); the --full line carries it as roofline.per_source")
+    ap.add_argument("--no-per-source", action="store_true", help="--full without the per-source leg of the default line")
+    ap.add_argument("--no-per-class", action="store_true", help="--full without roofline.per_class (the same sources with a filter per source: four classes of 64)")
+    ap.add_argument("--no-side", action="store_true", help="--full without roofline.side (configs 3, 5 and the block-streamed headline workload in the default line)")
+    ap.add_argument("--no-unscaled", action="store_true", help="--full without parity.unscaled / parity.vs_f64 (the same workload at amplitude 1, and both sides against the f64 response)")
     ap.add_argument("--shared-device", action="store_true", help="tiles by ticket although one rank runs (rh_rlm_set_exclusive(0)): what the N > 1 ranks do")
     ap.add_argument("--collective", default="auto", choices=["auto", "native", "native-reduce", "torch"],
                     help="the collective of the timed loop: native = rh_allreduce_sum_f32 of the C ABI (default for N > 1 when RCCL takes the ranks), native-reduce = rh_reduce_sum_f32 to rank 0, torch = torch.distributed")
     ap.add_argument("--baseline-sources", type=int, default=64, help="N > 1: sources of rank 0's shard the one-thread CPU baseline times")
-    ap.add_argument("--one-gpu-value", type=float, default=None, help="Msamples/s of this bench at --gpus 1: an N > 1 run then prints multi_gpu.efficiency_vs_1gpu")
+    ap.add_argument("--one-gpu-value", type=float, default=None, help="Msamples/s of this bench at --gpus 1: an N > 1 run with --full then prints multi_gpu.efficiency_vs_1gpu")
     ap.add_argument("--one-gpu-line", default=None, help="... or the 1-GPU JSON line itself / a file that holds it")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (f32; a fixed sample of an output over its share of 64 MB)")

@@ -78,7 +78,7 @@ def _free_port():
 def test_bench_two_ranks_time_sharing_one_device(G):
     env = dict(os.environ, RH_BENCH_ONE_DEVICE="1", RH_BENCH_NO_PMC="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--sources", "8", "--frames", "65536", "--no-autotune"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--sources", "8", "--frames", "65536", "--no-autotune", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -93,7 +93,7 @@ def test_bench_two_ranks_time_sharing_one_device(G):
 
 def test_bench_gpus_2_spawns_its_own_ranks_and_prints_a_complete_line(G):
     """`python bench.py --gpus 2` -- plain, no torch.distributed.run around it -- must start its ranks
-    itself, and the N > 1 line must carry parity against the ORACLE (not only against the ranks' own partials), the CPU
+    itself, and the N > 1 --full line must carry parity against the ORACLE (not only against the ranks' own partials), the CPU
     baseline, the roofline of the per-rank kernel with live traffic, and the ranks the communicator saw.  One GPU here, so
     the two ranks time-share it over gloo (RH_BENCH_ONE_DEVICE=1); the tiles of the kernel go by ticket as on the real node."""
     import shutil
@@ -101,7 +101,7 @@ def test_bench_gpus_2_spawns_its_own_ranks_and_prints_a_complete_line(G):
     env = dict(os.environ, RH_BENCH_ONE_DEVICE="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "RH_BENCH_NO_PMC"):  # (a caller's "no counter passes" is not this test's)
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--sources", "16", "--frames", "262144", "--baseline-sources", "4"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--sources", "16", "--frames", "262144", "--baseline-sources", "4", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -217,7 +217,7 @@ def test_bench_native_collective_at_one_gpu():
     import json
     import subprocess
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--collective", "native", "--sources", "32", "--frames", "65536", "--steps", "3", "--warmup", "1", "--no-per-source",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--collective", "native", "--sources", "32", "--frames", "65536", "--steps", "3", "--warmup", "1", "--full", "--no-per-source",
                         "--no-unscaled", "--no-autotune"], capture_output=True, text=True, timeout=600, env=dict(os.environ, RH_BENCH_NO_PMC="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
