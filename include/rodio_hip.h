@@ -610,6 +610,40 @@ rh_status rh_chirp_total_duration(uint32_t sample_rate, uint64_t total, uint64_t
 rh_status rh_chirp(float *dst, uint64_t first, uint64_t n, uint64_t total, uint32_t sample_rate, float start_frequency,
                    float end_frequency, uint64_t *out_n, rh_stream stream);
 
+/* ---- noise sources that start on the device: rodio's noise.rs (feature `noise`): WhiteUniform, WhiteTriangular, WhiteGaussian, Pink, Blue,
+ * Violet, Brownian, Red, Velvet -- mono, endless.  The noise is rh_dither's counter-based generator (above): h(seed, k) = mix(seed ^ mix(k + 1)),
+ * W(k) = u1(h(seed, k)); sample k (a u64, 0 at init, past 2^32 as needed) of a stream is
+ *   WHITE_UNIFORM W(k); WHITE_TRIANGULAR (u1 + u2) * 0.5; WHITE_GAUSSIAN rh_dither's GPDF (sigma 0.6) -- each of h(seed, k);
+ *   BLUE W(k) - W(k-1), W(-1) = 0; VIOLET B(k) - B(k-1), B = BLUE, B(-1) = 0;
+ *   PINK ((..((0 + v0) + v1) ..) + v15) / 16, v_i = 0 if k < 2^i, else W(D(m) + i), m = k & ~(2^i - 1), D(m) = sum_{j<16} floor((m-1) / 2^j)
+ *        (W indexed by draw number: noise.rs:491-512's counters in closed form);
+ *   VELVET(density) grid = ceil(rate as f32 / density as f32); cell c = k / grid, hc = h(seed, c): the impulse sits at
+ *        (u32(hc >> 32) * grid) >> 32, +1 if bit 31 of hc is set, else -1; every other sample +0.0;
+ *   RED acc = acc * leak + W(k); out = acc * scale, leak = 1 - (2 PI 5) / rate, scale = 1 / sqrt((s s) / (1 - leak leak)), s = sqrt(1/3);
+ *   BROWNIAN the same over WHITE_GAUSSIAN, s = 0.6.  (noise.rs:680-712; all f32.)
+ * The white kinds, blue, violet, pink and velvet are exact; the integrators run as a time-parallel scan, within 4e-5 absolute of the f64
+ * recurrence on the same white samples.
+ * init (host): the eight state words of a new stream -- [0..1] seed (lo, hi), [2..3] the next k (lo, hi) = 0, [4] kind, [5] velvet: grid
+ * (lo) / red, brownian: leak (f32 bits), [6] velvet: grid (hi) / red, brownian: scale (f32 bits), [7] acc (f32 bits) = 0.  An unknown
+ * kind, rate 0 or a velvet density of 0 (rodio's NonZero) is RH_ERR_INVALID.  try_seek is a host edit of the words: rodio's changes nothing
+ * but an integrator's acc, which it sets to 0 (noise.rs:795-799, 875-879); k is not moved.
+ * generate: row g of dst (dst + g * ld, ld >= n, any alignment) receives the next n samples of stream g < n_streams (<= 65535), whose eight
+ * words are states_dev[8g .. 8g+7] (a DEVICE array); any mix of kinds in one call.  k moves on by n and acc is carried on the device: the next
+ * call continues every stream.  A kind outside RH_NOISE_* gives NaN samples.  dst must not alias the states. */
+enum {
+    RH_NOISE_WHITE_UNIFORM = 0,
+    RH_NOISE_WHITE_TRIANGULAR = 1,
+    RH_NOISE_WHITE_GAUSSIAN = 2,
+    RH_NOISE_PINK = 3,
+    RH_NOISE_BLUE = 4,
+    RH_NOISE_VIOLET = 5,
+    RH_NOISE_BROWNIAN = 6,
+    RH_NOISE_RED = 7,
+    RH_NOISE_VELVET = 8
+};
+rh_status rh_noise_init(uint32_t state_host[8], int32_t kind, uint32_t sample_rate, uint64_t seed, uint32_t density);
+rh_status rh_noise_generate(float *dst, uint64_t ld, uint64_t n, uint32_t *states_dev, uint32_t n_streams, rh_stream stream);
+
 /* ---- multi-GPU: one process per GPU, sources sharded over the ranks, the mixer sum (src/mixer.rs:185-198 is the
  * only place rodio's streams meet) completed by ONE collective per mixed block over RCCL / xGMI.  Rank 0 calls
  * rh_comm_unique_id and hands the 128 bytes to the other ranks (any out-of-band channel); every rank then calls

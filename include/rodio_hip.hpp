@@ -35,6 +35,7 @@
 #include <mutex>
 #include <numeric>
 #include <optional>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -1177,6 +1178,224 @@ private:
     std::uint32_t rate_;
     float f0_, f1_;
     std::uint64_t total_ = 0, i_ = 0, pulled_ = 0;  // i_: the next sample produced; pulled_: the next one read() hands out in deferred mode
+};
+
+// ---------------------------------------------------------------- noise sources that start on the device ----
+namespace detail {
+/// The noise contract of rodio_hip.h (rh_noise_init / rh_noise_generate), restated on the host for next().  The white kinds, blue,
+/// violet, pink and velvet are the device's bits; the Gaussian's logf / cosf are the host's; the integrators run rodio's SERIAL f32
+/// recurrence here (the device runs a time-parallel scan within 4e-5 of the f64 recurrence).
+namespace noise {
+inline std::uint64_t mix(std::uint64_t z) {
+    z ^= z >> 30;
+    z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27;
+    z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+inline std::uint64_t hash(std::uint64_t seed, std::uint64_t k) { return mix(seed ^ mix(k + 1)); }
+inline float u1(std::uint64_t h) { return (float)((std::int32_t)(h >> 40) - 8388608) * 1.1920928955078125e-07f; }
+inline float u2(std::uint64_t h) { return (float)((std::int32_t)((h >> 16) & 0xffffffu) - 8388608) * 1.1920928955078125e-07f; }
+inline float gaussian(std::uint64_t h) {
+    const float a = (float)((std::uint32_t)(h >> 40) + 1u) * 5.9604644775390625e-08f;
+    const float b = (float)((std::uint32_t)(h >> 16) & 0xffffffu) * 5.9604644775390625e-08f;
+    return std::sqrt(-2.0f * std::log(a)) * std::cos(6.2831853071795864769f * b) * 0.6f;
+}
+inline float white(std::uint64_t seed, std::uint64_t k) { return u1(hash(seed, k)); }
+inline float blue(std::uint64_t seed, std::uint64_t k) { return white(seed, k) - (k ? white(seed, k - 1) : 0.0f); }
+inline std::uint64_t pink_draws_before(std::uint64_t m) {  // D(m) = sum_{j<16} floor((m-1) / 2^j)
+    const std::uint64_t x = m - 1, y = x >> 16;
+    return (2 * x - (std::uint64_t)__builtin_popcountll(x)) - (2 * y - (std::uint64_t)__builtin_popcountll(y));
+}
+inline float pink(std::uint64_t seed, std::uint64_t k) {
+    float sum = 0.0f;
+    for (int i = 0; i < 16; ++i) {
+        const std::uint64_t m = k & ~((1ull << i) - 1);
+        sum += m == 0 ? 0.0f : white(seed, pink_draws_before(m) + (std::uint64_t)i);
+    }
+    return sum / 16.0f;
+}
+inline float velvet(std::uint64_t seed, std::uint64_t k, std::uint64_t grid) {
+    const std::uint64_t c = k / grid, hc = hash(seed, c);
+    return k - c * grid == (((hc >> 32) * grid) >> 32) ? ((hc & 0x80000000ull) ? 1.0f : -1.0f) : 0.0f;
+}
+}  // namespace noise
+}  // namespace detail
+
+/// noise.rs's nine generators (RH_NOISE_*)
+enum class NoiseKind : std::int32_t {
+    WhiteUniform = RH_NOISE_WHITE_UNIFORM,
+    WhiteTriangular = RH_NOISE_WHITE_TRIANGULAR,
+    WhiteGaussian = RH_NOISE_WHITE_GAUSSIAN,
+    Pink = RH_NOISE_PINK,
+    Blue = RH_NOISE_BLUE,
+    Violet = RH_NOISE_VIOLET,
+    Brownian = RH_NOISE_BROWNIAN,
+    Red = RH_NOISE_RED,
+    Velvet = RH_NOISE_VELVET
+};
+constexpr std::uint32_t kVelvetDefaultDensity = 2000;  // VELVET_DEFAULT_DENSITY (noise.rs:434)
+/// A seed from the OS entropy source: what new(rate) uses where rodio seeds its SmallRng with rand::make_rng().
+inline std::uint64_t entropy_seed() {
+    std::random_device rd;
+    return ((std::uint64_t)rd() << 32) ^ (std::uint64_t)rd();
+}
+
+/// One of noise.rs's sources (src/source/noise.rs): mono, endless (size_hint (usize::MAX, None)), no spans, no total duration.  Its eight
+/// state words (rodio_hip.h, rh_noise_init) live on the host and, once the source has filled device memory, on the device, which then
+/// carries them: the host's k follows every fill, and an integrator's acc is read back from the device before the host next() needs it.
+/// try_seek changes nothing but an integrator's acc (set to 0, noise.rs:795-799, 875-879).  A bad kind, rate 0 or density 0 throws.
+class NoiseSource : public DeviceGenerator {
+public:
+    NoiseSource(NoiseKind kind, std::uint32_t sample_rate, std::uint64_t seed, std::uint32_t density = kVelvetDefaultDensity) : kind_(kind), rate_(sample_rate) {
+        check(rh_noise_init(st_, (std::int32_t)kind, sample_rate, seed, density), "rh_noise_init: unknown kind, sample rate 0 or density 0");
+    }
+    std::optional<float> next() override {
+        pull_state();
+        const std::uint64_t seed = (std::uint64_t)st_[0] | ((std::uint64_t)st_[1] << 32), k = this->k();
+        float v;
+        switch (kind_) {
+            case NoiseKind::WhiteUniform: v = detail::noise::u1(detail::noise::hash(seed, k)); break;
+            case NoiseKind::WhiteTriangular: {
+                const std::uint64_t h = detail::noise::hash(seed, k);
+                v = (detail::noise::u1(h) + detail::noise::u2(h)) * 0.5f;
+                break;
+            }
+            case NoiseKind::WhiteGaussian: v = detail::noise::gaussian(detail::noise::hash(seed, k)); break;
+            case NoiseKind::Pink: v = detail::noise::pink(seed, k); break;
+            case NoiseKind::Blue: v = detail::noise::blue(seed, k); break;
+            case NoiseKind::Violet: v = detail::noise::blue(seed, k) - (k ? detail::noise::blue(seed, k - 1) : 0.0f); break;
+            case NoiseKind::Velvet: v = detail::noise::velvet(seed, k, (std::uint64_t)st_[5] | ((std::uint64_t)st_[6] << 32)); break;
+            default: {  // Brownian, Red: noise.rs:705-711, multiply then add
+                const std::uint64_t h = detail::noise::hash(seed, k);
+                const float w = kind_ == NoiseKind::Brownian ? detail::noise::gaussian(h) : detail::noise::u1(h);
+                const float acc = word_f(7) * word_f(5) + w;
+                set_word_f(7, acc);
+                v = acc * word_f(6);
+            }
+        }
+        set_k(k + 1);
+        dev_dirty_ = true;
+        return v;
+    }
+    std::size_t read(float *dst, std::size_t n) override {
+        if (defer_) return n;
+        return Source::read(dst, n);
+    }
+    std::uint16_t channels() const override { return 1; }
+    std::uint32_t sample_rate() const override { return rate_; }
+    std::optional<std::size_t> current_span_len() const override { return std::nullopt; }
+    std::optional<Nanos> total_duration() const override { return std::nullopt; }
+    SizeHint size_hint() const override { return SizeHint{SIZE_MAX, std::nullopt}; }
+    bool try_seek(Nanos) override {
+        if (kind_ == NoiseKind::Brownian || kind_ == NoiseKind::Red) {
+            pull_state();
+            set_word_f(7, 0.0f);
+            dev_dirty_ = true;
+        }
+        return true;
+    }
+    std::size_t fill_device(float *ddst, std::size_t n, rh_stream stream) override {
+        if (!n) return 0;
+        if (dev_dirty_) {  // the eight words go up at the start and after the host has moved them (next(), a seek)
+            dev_.reset(8);
+            check(rh_memcpy_h2d(dev_.get(), st_, sizeof st_, stream), "rh_memcpy_h2d");
+            check(rh_stream_synchronize(stream), "rh_stream_synchronize");
+            dev_dirty_ = false;
+        }
+        check(rh_noise_generate(ddst, n, n, reinterpret_cast<std::uint32_t *>(dev_.get()), 1, stream), "rh_noise_generate");
+        set_k(k() + n);  // the host's k follows the device's; an integrator's acc is fetched when the host needs it
+        if (kind_ == NoiseKind::Brownian || kind_ == NoiseKind::Red) acc_on_device_ = true;
+        stream_ = stream;
+        return n;
+    }
+    NoiseKind kind() const { return kind_; }
+    /// The u64 index of the next sample.
+    std::uint64_t k() const { return (std::uint64_t)st_[2] | ((std::uint64_t)st_[3] << 32); }
+    /// The stream's eight state words (rodio_hip.h), with the device's acc.
+    const std::uint32_t *state() {
+        pull_state();
+        return st_;
+    }
+
+protected:
+    /// WhiteUniform::std_dev (noise.rs:157), WhiteTriangular's (:217), WhiteGaussian's (:371)
+    static float uniform_std_dev() { return std::sqrt(1.0f / 3.0f); }
+    static float triangular_std_dev() { return 2.0f / std::sqrt(6.0f); }
+
+private:
+    float word_f(int q) const {
+        float f;
+        std::memcpy(&f, &st_[q], 4);
+        return f;
+    }
+    void set_word_f(int q, float f) { std::memcpy(&st_[q], &f, 4); }
+    void set_k(std::uint64_t k) { st_[2] = (std::uint32_t)k, st_[3] = (std::uint32_t)(k >> 32); }
+    void pull_state() {
+        if (!acc_on_device_) return;
+        std::uint32_t w = 0;
+        check(rh_memcpy_d2h(&w, dev_.get() + 7, 4, stream_), "rh_memcpy_d2h");
+        check(rh_stream_synchronize(stream_), "rh_stream_synchronize");
+        st_[7] = w;
+        acc_on_device_ = false;
+    }
+    NoiseKind kind_;
+    std::uint32_t rate_;
+    std::uint32_t st_[8] = {};
+    detail::DeviceBuf dev_;
+    bool dev_dirty_ = true, acc_on_device_ = false;
+    rh_stream stream_ = nullptr;
+};
+/// WhiteUniform: uniform in [-1, 1) (noise.rs:142-170)
+struct WhiteUniform : NoiseSource {
+    explicit WhiteUniform(std::uint32_t rate) : WhiteUniform(rate, entropy_seed()) {}
+    WhiteUniform(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::WhiteUniform, rate, seed) {}
+    float std_dev() const { return uniform_std_dev(); }
+};
+/// WhiteTriangular: triangular in (-1, 1), mode 0 (noise.rs:203-230)
+struct WhiteTriangular : NoiseSource {
+    explicit WhiteTriangular(std::uint32_t rate) : WhiteTriangular(rate, entropy_seed()) {}
+    WhiteTriangular(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::WhiteTriangular, rate, seed) {}
+    float std_dev() const { return triangular_std_dev(); }
+};
+/// WhiteGaussian: normal, mean 0, sigma 0.6 (noise.rs:383-412)
+struct WhiteGaussian : NoiseSource {
+    explicit WhiteGaussian(std::uint32_t rate) : WhiteGaussian(rate, entropy_seed()) {}
+    WhiteGaussian(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::WhiteGaussian, rate, seed) {}
+    float mean() const { return 0.0f; }
+    float std_dev() const { return 0.6f; }
+};
+/// Pink: Voss-McCartney over 16 generators (noise.rs:472-512)
+struct Pink : NoiseSource {
+    explicit Pink(std::uint32_t rate) : Pink(rate, entropy_seed()) {}
+    Pink(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::Pink, rate, seed) {}
+};
+/// Blue: the first difference of white (noise.rs:570-583)
+struct Blue : NoiseSource {
+    explicit Blue(std::uint32_t rate) : Blue(rate, entropy_seed()) {}
+    Blue(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::Blue, rate, seed) {}
+};
+/// Violet: the first difference of blue (noise.rs:638-651)
+struct Violet : NoiseSource {
+    explicit Violet(std::uint32_t rate) : Violet(rate, entropy_seed()) {}
+    Violet(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::Violet, rate, seed) {}
+};
+/// Brownian: the leaky integral of WhiteGaussian (noise.rs:749-757)
+struct Brownian : NoiseSource {
+    explicit Brownian(std::uint32_t rate) : Brownian(rate, entropy_seed()) {}
+    Brownian(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::Brownian, rate, seed) {}
+};
+/// Red: the leaky integral of WhiteUniform (noise.rs:832-840)
+struct Red : NoiseSource {
+    explicit Red(std::uint32_t rate) : Red(rate, entropy_seed()) {}
+    Red(std::uint32_t rate, std::uint64_t seed) : NoiseSource(NoiseKind::Red, rate, seed) {}
+};
+/// Velvet: one +-1 impulse per cell of ceil(rate / density) samples (noise.rs:282-330); density 0 throws (NonZero)
+struct Velvet : NoiseSource {
+    explicit Velvet(std::uint32_t rate) : Velvet(rate, kVelvetDefaultDensity, entropy_seed()) {}
+    Velvet(std::uint32_t rate, std::uint64_t seed) : Velvet(rate, kVelvetDefaultDensity, seed) {}
+    Velvet(std::uint32_t rate, std::uint32_t density, std::uint64_t seed) : NoiseSource(NoiseKind::Velvet, rate, seed, density) {}
 };
 
 // ---------------------------------------------------------------- parameters that change while a source plays ----

@@ -20,6 +20,20 @@ from .source import (  # noqa: F401
     TriangleWave,
     chirp,
     signal_phase_advance,
+    NoiseBank,
+    NoiseSource,
+    WhiteUniform,
+    WhiteTriangular,
+    WhiteGaussian,
+    Pink,
+    Blue,
+    Violet,
+    Brownian,
+    Red,
+    Velvet,
+    noise_state,
+    white,
+    pink,
     GpuSource,
     Mixer,
     ResampleLowpassMix,

@@ -199,6 +199,8 @@ SIGNATURES = {
     "rh_chirp_total_samples": (i32, [u32, u64, C.POINTER(u64)]),
     "rh_chirp_total_duration": (i32, [u32, u64, C.POINTER(u64), C.POINTER(u32)]),
     "rh_chirp": (i32, [vp, u64, u64, u64, u32, f32, f32, C.POINTER(u64), vp]),
+    "rh_noise_init": (i32, [C.POINTER(u32), i32, u32, u64, u32]),
+    "rh_noise_generate": (i32, [vp, u64, u64, vp, u32, vp]),
 }
 
 

@@ -9,6 +9,7 @@
 // Streaming kernels, HBM-bound: one element per lane per grid-stride step (the 8-byte types move
 // 512 B per wave-instruction).
 #include "rh_common.h"
+#include "rh_noise.h"
 
 namespace {
 
@@ -65,36 +66,22 @@ __global__ __launch_bounds__(kBlock) void k_distortion(float *__restrict__ dst, 
 // noise from a SmallRng seeded from system entropy (noise.rs:137,198,378,554), so no two runs of it agree; the
 // contract here is a counter-based generator: the noise of sample k is a pure function of (seed, k), which makes
 // the op stateless and any block split reproduce one pass.  Distributions as in noise.rs: uniform [-1,1] (:146),
-// triangular (-1,1) mode 0 (:206), normal sigma 0.6 (:394), blue = white[k] - white[k - channels] per channel (:579).
-__device__ __forceinline__ uint64_t dither_bits(uint64_t seed, uint64_t k) {
-    auto mix = [](uint64_t z) {  // splitmix64 finaliser
-        z ^= z >> 30;
-        z *= 0xbf58476d1ce4e5b9ull;
-        z ^= z >> 27;
-        z *= 0x94d049bb133111ebull;
-        z ^= z >> 31;
-        return z;
-    };
-    return mix(seed ^ mix(k + 1));
-}
-__device__ __forceinline__ float dither_u1(uint64_t h) { return (float)((int32_t)(h >> 40) - 8388608) * 1.1920928955078125e-07f; }              // 24 bits -> [-1, 1)
-__device__ __forceinline__ float dither_u2(uint64_t h) { return (float)((int32_t)((h >> 16) & 0xffffffu) - 8388608) * 1.1920928955078125e-07f; }
+// triangular (-1,1) mode 0 (:206), normal sigma 0.6 (:394), blue = white[k] - white[k - channels] per channel (:579).  The generator and
+// the four distributions are rh_noise.h's, shared with the noise sources (rh_noise.hip).
 __global__ __launch_bounds__(kBlock) void k_dither(float *__restrict__ dst, const float *__restrict__ src, size_t n, uint64_t k0, uint32_t channels, float lsb, int32_t algorithm, uint64_t seed, int vec_ok) {
     rh::map4<kBlock>(dst, src, n, vec_ok, [=](size_t i, float x) {
         const uint64_t k = k0 + i;
-        const uint64_t h = dither_bits(seed, k);
+        const uint64_t h = rhnoise::hash(seed, k);
         float noise;
-        if (algorithm == 3) {  // TPDF
-            noise = (dither_u1(h) + dither_u2(h)) * 0.5f;
-        } else if (algorithm == 2) {  // RPDF
-            noise = dither_u1(h);
-        } else if (algorithm == 1) {  // HighPass: the channel's previous white sample is the one a frame earlier
-            const float prev = k >= channels ? dither_u1(dither_bits(seed, k - channels)) : 0.0f;
-            noise = dither_u1(h) - prev;
-        } else {  // GPDF: Box-Muller on the two 24-bit fields
-            const float a = (float)((uint32_t)(h >> 40) + 1u) * 5.9604644775390625e-08f;       // (0, 1]
-            const float b = (float)((uint32_t)(h >> 16) & 0xffffffu) * 5.9604644775390625e-08f;  // [0, 1)
-            noise = sqrtf(-2.0f * logf(a)) * cosf(6.2831853071795864769f * b) * 0.6f;
+        if (algorithm == 3) {  // TPDF = WhiteTriangular
+            noise = rhnoise::triangular(h);
+        } else if (algorithm == 2) {  // RPDF = WhiteUniform
+            noise = rhnoise::u1(h);
+        } else if (algorithm == 1) {  // HighPass = Blue: the channel's previous white sample is the one a frame earlier
+            const float prev = k >= channels ? rhnoise::white(seed, k - channels) : 0.0f;
+            noise = rhnoise::u1(h) - prev;
+        } else {  // GPDF = WhiteGaussian: Box-Muller on the two 24-bit fields
+            noise = rhnoise::gaussian(h);
         }
         return x - noise * lsb;
     });

@@ -1060,3 +1060,211 @@ class Chirp:
 
 def chirp(sample_rate: int, start_frequency: float, end_frequency: float, duration_ns: int) -> Chirp:
     return Chirp(sample_rate, start_frequency, end_frequency, duration_ns)
+
+
+# ---- noise sources that start on the device: rodio's noise.rs (rh_noise_init / rh_noise_generate) -------------------------------
+NOISE_KINDS = {"white_uniform": 0, "white_triangular": 1, "white_gaussian": 2, "pink": 3, "blue": 4, "violet": 5, "brownian": 6, "red": 7, "velvet": 8}
+VELVET_DEFAULT_DENSITY = 2000  # noise.rs:434
+_INTEGRATORS = (NOISE_KINDS["brownian"], NOISE_KINDS["red"])
+
+
+def _noise_kind(k) -> int:
+    code = NOISE_KINDS.get(k.lower(), k) if isinstance(k, str) else int(k)
+    if code not in NOISE_KINDS.values():
+        raise ValueError(f"unknown noise kind {k!r}: one of {sorted(NOISE_KINDS)}")
+    return code
+
+
+def entropy_seed() -> int:
+    """A u64 from the OS entropy source: what new(rate) seeds with, where rodio calls rand::make_rng()."""
+    import os
+
+    return int.from_bytes(os.urandom(8), "little")
+
+
+def noise_state(kind, sample_rate: int, seed: int, density: int = VELVET_DEFAULT_DENSITY) -> np.ndarray:
+    """rh_noise_init: the eight u32 state words of a new stream (rodio_hip.h).  Unknown kind, rate 0, density 0: RhError."""
+    st = (C.c_uint32 * 8)()
+    check(lib.rh_noise_init(st, _noise_kind(kind), int(sample_rate), int(seed) & ((1 << 64) - 1), int(density)),
+          "rh_noise_init (unknown kind, sample rate 0 or velvet density 0)")
+    return np.frombuffer(st, dtype=np.uint32).copy()
+
+
+class NoiseBank:
+    """G noise streams of any kinds whose state (rodio_hip.h's eight words each) lives in device memory.  take(n) fills a [G, n] device
+    tensor, row g with stream g's next n samples, and moves every stream on (k, and an integrator's acc): the next take continues
+    them.  Nothing is uploaded.  seeds None: one from the OS entropy source per stream."""
+
+    def __init__(self, kinds, sample_rates, seeds=None, densities=None):
+        torch = _t()
+        _ensure()
+        kinds = list(kinds) if isinstance(kinds, (list, tuple)) else [kinds]
+        g = len(kinds)
+        rates = [int(r) for r in (sample_rates if hasattr(sample_rates, "__len__") else [sample_rates] * g)]
+        seeds = [entropy_seed() for _ in range(g)] if seeds is None else [int(s) for s in (seeds if hasattr(seeds, "__len__") else [seeds] * g)]
+        dens = [VELVET_DEFAULT_DENSITY] * g if densities is None else [int(d) for d in (densities if hasattr(densities, "__len__") else [densities] * g)]
+        if not (len(rates) == len(seeds) == len(dens) == g) or g == 0:
+            raise ValueError("one kind, sample rate, seed (and density) per stream")
+        self.kinds = [_noise_kind(k) for k in kinds]
+        self.rates, self.seeds, self.densities = rates, seeds, dens
+        st = np.concatenate([noise_state(k, r, s, d) for k, r, s, d in zip(self.kinds, rates, seeds, dens)])
+        self.state = torch.from_numpy(st.view(np.int32)).cuda()
+
+    def __len__(self):
+        return len(self.kinds)
+
+    def take(self, n: int, out=None):
+        torch = _t()
+        g = len(self)
+        if out is None:
+            out = torch.empty((g, max(int(n), 1)), dtype=torch.float32, device="cuda")
+        if out.dim() != 2 or out.shape[0] != g or out.shape[1] < n or out.stride(1) != 1 or out.dtype != torch.float32:
+            raise ValueError("out must be a float32 [G, >= n] with contiguous rows")
+        check(lib.rh_noise_generate(_ptr(out), out.stride(0), int(n), _ptr(self.state), g, _stream()), "rh_noise_generate")
+        return out[:, : int(n)]
+
+    def states(self) -> np.ndarray:
+        """[G, 8] u32: the streams' state words as the device holds them."""
+        return self.state.view(-1, 8).cpu().numpy().view(np.uint32)
+
+    def positions(self) -> np.ndarray:
+        s = self.states().astype(np.uint64)
+        return s[:, 2] | (s[:, 3] << np.uint64(32))
+
+    def try_seek(self, pos_ns: int = 0):
+        """Every stream's try_seek(pos): Ok, and nothing moves but an integrator's acc, which goes to 0 (noise.rs:795-799, 875-879)."""
+        torch = _t()
+        rows = [g for g, k in enumerate(self.kinds) if k in _INTEGRATORS]
+        if rows:
+            self.state.view(-1, 8)[torch.tensor(rows, device="cuda"), 7] = 0
+
+
+class NoiseSource:
+    """One of rodio's noise sources on the device (noise.rs): take(n) returns its next n samples as a device tensor (source(n): as a
+    mono GpuSource).  Mono, endless: size_hint (usize::MAX, None), no span length, no total duration.  seed None: from the OS
+    entropy source (rodio's new); new_with_seed(rate, seed) is the reproducible form."""
+
+    KIND = None
+
+    def __init__(self, sample_rate: int, seed=None, density: int = VELVET_DEFAULT_DENSITY, kind=None):
+        kind = self.KIND if kind is None else kind
+        self._bank = NoiseBank([kind], [sample_rate], None if seed is None else [seed], [density])
+
+    @classmethod
+    def new(cls, sample_rate: int):
+        return cls(sample_rate)
+
+    @classmethod
+    def new_with_seed(cls, sample_rate: int, seed: int):
+        return cls(sample_rate, seed)
+
+    @property
+    def seed(self) -> int:
+        return self._bank.seeds[0]
+
+    def channels(self) -> int:
+        return 1
+
+    def sample_rate(self) -> int:
+        return self._bank.rates[0]
+
+    def current_span_len(self):
+        return None
+
+    def total_duration(self):
+        return None
+
+    def size_hint(self):
+        return (USIZE_MAX, None)
+
+    def position(self) -> int:
+        return int(self._bank.positions()[0])
+
+    def take(self, n: int):
+        return self._bank.take(n)[0]
+
+    def source(self, n: int) -> GpuSource:
+        return GpuSource(self.take(n), 1, self.sample_rate())
+
+    def try_seek(self, pos_ns: int = 0):
+        self._bank.try_seek(pos_ns)
+
+
+class WhiteUniform(NoiseSource):
+    """Uniform in [-1, 1) (noise.rs:142-170)."""
+    KIND = "white_uniform"
+
+    def std_dev(self) -> float:
+        return float(np.sqrt(np.float32(1.0) / np.float32(3.0)))
+
+
+class WhiteTriangular(NoiseSource):
+    """Triangular in (-1, 1), mode 0 (noise.rs:203-230)."""
+    KIND = "white_triangular"
+
+    def std_dev(self) -> float:
+        return float(np.float32(2.0) / np.sqrt(np.float32(6.0)))
+
+
+class WhiteGaussian(NoiseSource):
+    """Normal, mean 0, sigma 0.6 (noise.rs:383-412): rh_dither's GPDF noise."""
+    KIND = "white_gaussian"
+
+    def mean(self) -> float:
+        return 0.0
+
+    def std_dev(self) -> float:
+        return float(np.float32(0.6))
+
+
+class Pink(NoiseSource):
+    """Voss-McCartney over 16 generators (noise.rs:472-512)."""
+    KIND = "pink"
+
+
+class Blue(NoiseSource):
+    """The first difference of white (noise.rs:570-583)."""
+    KIND = "blue"
+
+
+class Violet(NoiseSource):
+    """The first difference of blue (noise.rs:638-651)."""
+    KIND = "violet"
+
+
+class Brownian(NoiseSource):
+    """The leaky integral of WhiteGaussian (noise.rs:749-757); try_seek sets its accumulator to 0."""
+    KIND = "brownian"
+
+
+class Red(NoiseSource):
+    """The leaky integral of WhiteUniform (noise.rs:832-840); try_seek sets its accumulator to 0."""
+    KIND = "red"
+
+
+class Velvet(NoiseSource):
+    """One +-1 impulse per cell of ceil(rate / density) samples (noise.rs:282-330).  Density 0 raises RhError (rodio's NonZero)."""
+    KIND = "velvet"
+
+    def __init__(self, sample_rate: int, seed=None, density: int = VELVET_DEFAULT_DENSITY):
+        super().__init__(sample_rate, seed, density)
+
+    @classmethod
+    def new_with_density(cls, sample_rate: int, density: int, seed=None):
+        return cls(sample_rate, seed, density)
+
+
+def white(sample_rate: int) -> WhiteUniform:
+    """Deprecated as in rodio 0.21 (noise.rs:56-60): use WhiteUniform(rate)."""
+    import warnings
+
+    warnings.warn("white() is deprecated: use WhiteUniform(sample_rate)", DeprecationWarning, stacklevel=2)
+    return WhiteUniform(sample_rate)
+
+
+def pink(sample_rate: int) -> Pink:
+    """Deprecated as in rodio 0.21 (noise.rs:62-66): use Pink(rate)."""
+    import warnings
+
+    warnings.warn("pink() is deprecated: use Pink(sample_rate)", DeprecationWarning, stacklevel=2)
+    return Pink(sample_rate)

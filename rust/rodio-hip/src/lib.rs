@@ -2335,3 +2335,167 @@ impl Source for GpuChirp {
     }
 }
 impl Drop for GpuChirp { fn drop(&mut self) { unsafe { rh_stream_synchronize(self.stream); rh_stream_destroy(self.stream); } } }
+
+// ------------------------------------------------------------------------------------------------ noise sources ----
+/// noise.rs's nine generators, numbered as `RH_NOISE_*`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum NoiseKind { WhiteUniform = 0, WhiteTriangular = 1, WhiteGaussian = 2, Pink = 3, Blue = 4, Violet = 5, Brownian = 6, Red = 7, Velvet = 8 }
+
+/// `VELVET_DEFAULT_DENSITY` (`noise.rs:434`).
+pub const VELVET_DEFAULT_DENSITY: u32 = 2000;
+
+/// A seed for `new(rate)`, where rodio seeds a `SmallRng` from the OS (`rand::make_rng()`): std's `RandomState` draws its keys from the OS
+/// entropy source once per process and moves them on for every new one.
+pub fn entropy_seed() -> u64 {
+    use std::hash::BuildHasher;
+    std::collections::hash_map::RandomState::new().hash_one(0x6e6f697365u64)
+}
+
+/// One of noise.rs's sources on the device (`rh_noise_init` / `rh_noise_generate`): mono, endless, no spans, no total duration.  The
+/// eight state words (rodio_hip.h) live on the device once the source has made samples there; `next()` serves blocks the device made,
+/// copied back through page-locked memory.  `try_seek` is Ok and changes nothing but an integrator's accumulator, which goes to 0
+/// (`noise.rs:795-799, 875-879`); what `next()` had made ahead is dropped and the stream goes on from the next sample it had not served.
+pub struct GpuNoise { kind: NoiseKind, rate: u32, state: [u32; 8], dev: DeviceBuf, dirty: bool, stream: RhStream, block: PinnedBuf, dblock: DeviceBuf,
+                      pos: usize, len: usize }
+unsafe impl Send for GpuNoise {}
+impl GpuNoise {
+    const BLOCK: usize = 1 << 15;
+    /// Panics for rate 0 or a velvet density of 0 (rodio's `NonZero`).
+    pub fn with_seed(kind: NoiseKind, sample_rate: SampleRate, seed: u64, density: u32) -> Self {
+        let mut state = [0u32; 8];
+        ck(unsafe { rh_noise_init(state.as_mut_ptr(), kind as i32, sample_rate.get(), seed, density) }, "rh_noise_init: density must be > 0");
+        let mut stream: RhStream = ptr::null_mut();
+        ck(unsafe { rh_stream_create(&mut stream) }, "rh_stream_create");
+        GpuNoise { kind, rate: sample_rate.get(), state, dev: DeviceBuf::new(), dirty: true, stream, block: PinnedBuf::new(), dblock: DeviceBuf::new(), pos: 0, len: 0 }
+    }
+    pub fn kind(&self) -> NoiseKind { self.kind }
+    /// The u64 index of the next sample the device makes.
+    fn k(&self) -> u64 { self.state[2] as u64 | (self.state[3] as u64) << 32 }
+    fn set_k(&mut self, k: u64) { self.state[2] = k as u32; self.state[3] = (k >> 32) as u32; }
+    fn upload_state(&mut self, stream: RhStream) {
+        if !self.dirty { return; }
+        self.dev.reserve(8);
+        unsafe {
+            ck(rh_memcpy_h2d(self.dev.p.cast(), self.state.as_ptr().cast(), 32, stream), "rh_memcpy_h2d");
+            ck(rh_stream_synchronize(stream), "rh_stream_synchronize");
+        }
+        self.dirty = false;
+    }
+    fn is_integrator(&self) -> bool { matches!(self.kind, NoiseKind::Brownian | NoiseKind::Red) }
+}
+impl DeviceGenerator for GpuNoise {
+    fn fill_device(&mut self, ddst: *mut f32, n: usize, stream: RhStream) -> usize {
+        if n == 0 { return 0; }
+        self.upload_state(stream);
+        ck(unsafe { rh_noise_generate(ddst, n as u64, n as u64, self.dev.p.cast(), 1, stream) }, "rh_noise_generate");
+        let k = self.k() + n as u64;  // the host's k goes on with the device's (the accumulator stays there)
+        self.set_k(k);
+        n
+    }
+}
+impl Iterator for GpuNoise {
+    type Item = f32;
+    fn next(&mut self) -> Option<f32> {
+        if self.pos == self.len {
+            let n = Self::BLOCK;
+            self.block.reserve(n);
+            self.dblock.reserve(n);
+            let (d, s) = (self.dblock.p, self.stream);
+            self.fill_device(d, n, s);
+            unsafe {
+                ck(rh_memcpy_d2h(self.block.p.cast(), d.cast(), n * 4, s), "rh_memcpy_d2h");
+                ck(rh_stream_synchronize(s), "rh_stream_synchronize");
+            }
+            self.pos = 0;
+            self.len = n;
+        }
+        let v = unsafe { *self.block.p.add(self.pos) };
+        self.pos += 1;
+        Some(v)
+    }
+    fn size_hint(&self) -> (usize, Option<usize>) { (usize::MAX, None) }
+}
+impl Source for GpuNoise {
+    fn current_span_len(&self) -> Option<usize> { None }
+    fn channels(&self) -> ChannelCount { ChannelCount::new(1).unwrap() }
+    fn sample_rate(&self) -> SampleRate { SampleRate::new(self.rate).unwrap() }
+    fn total_duration(&self) -> Option<Duration> { None }
+    fn try_seek(&mut self, _pos: Duration) -> Result<(), SeekError> {
+        let unserved = (self.len - self.pos) as u64;
+        if unserved > 0 || self.is_integrator() {
+            if !self.dirty {  // the device's words are the current ones: fetch them (the accumulator lives there)
+                unsafe {
+                    ck(rh_memcpy_d2h(self.state.as_mut_ptr().cast(), self.dev.p.cast(), 32, self.stream), "rh_memcpy_d2h");
+                    ck(rh_stream_synchronize(self.stream), "rh_stream_synchronize");
+                }
+            }
+            let k = self.k() - unserved;
+            self.set_k(k);
+            if self.is_integrator() { self.state[7] = 0; }
+            self.dirty = true;
+        }
+        self.pos = 0;
+        self.len = 0;
+        Ok(())
+    }
+}
+impl Drop for GpuNoise { fn drop(&mut self) { unsafe { rh_stream_synchronize(self.stream); rh_stream_destroy(self.stream); } } }
+
+macro_rules! noise_type {
+    ($(#[$doc:meta])* $name:ident, $kind:expr) => {
+        $(#[$doc])*
+        pub struct $name(GpuNoise);
+        impl $name {
+            /// Seeded from the OS entropy source, as rodio's `new`.
+            pub fn new(sample_rate: SampleRate) -> Self { Self::new_with_seed(sample_rate, entropy_seed()) }
+            /// The reproducible form: the same seed gives the same stream.
+            pub fn new_with_seed(sample_rate: SampleRate, seed: u64) -> Self { $name(GpuNoise::with_seed($kind, sample_rate, seed, VELVET_DEFAULT_DENSITY)) }
+            pub fn inner(&self) -> &GpuNoise { &self.0 }
+        }
+        impl DeviceGenerator for $name {
+            fn fill_device(&mut self, ddst: *mut f32, n: usize, stream: RhStream) -> usize { self.0.fill_device(ddst, n, stream) }
+        }
+        impl Iterator for $name {
+            type Item = f32;
+            fn next(&mut self) -> Option<f32> { self.0.next() }
+            fn size_hint(&self) -> (usize, Option<usize>) { self.0.size_hint() }
+        }
+        impl Source for $name {
+            fn current_span_len(&self) -> Option<usize> { None }
+            fn channels(&self) -> ChannelCount { self.0.channels() }
+            fn sample_rate(&self) -> SampleRate { self.0.sample_rate() }
+            fn total_duration(&self) -> Option<Duration> { None }
+            fn try_seek(&mut self, pos: Duration) -> Result<(), SeekError> { self.0.try_seek(pos) }
+        }
+    };
+}
+noise_type!(/// `WhiteUniform` (`noise.rs:142-170`): uniform in [-1, 1).
+            GpuWhiteUniform, NoiseKind::WhiteUniform);
+noise_type!(/// `WhiteTriangular` (`noise.rs:203-230`): triangular in (-1, 1), mode 0.
+            GpuWhiteTriangular, NoiseKind::WhiteTriangular);
+noise_type!(/// `WhiteGaussian` (`noise.rs:383-412`): normal, mean 0, sigma 0.6.
+            GpuWhiteGaussian, NoiseKind::WhiteGaussian);
+noise_type!(/// `Pink` (`noise.rs:472-512`): Voss-McCartney over 16 generators.
+            GpuPink, NoiseKind::Pink);
+noise_type!(/// `Blue` (`noise.rs:570-583`): the first difference of white.
+            GpuBlue, NoiseKind::Blue);
+noise_type!(/// `Violet` (`noise.rs:638-651`): the first difference of blue.
+            GpuViolet, NoiseKind::Violet);
+noise_type!(/// `Brownian` (`noise.rs:749-757`): the leaky integral of `WhiteGaussian`.
+            GpuBrownian, NoiseKind::Brownian);
+noise_type!(/// `Red` (`noise.rs:832-840`): the leaky integral of `WhiteUniform`.
+            GpuRed, NoiseKind::Red);
+noise_type!(/// `Velvet` (`noise.rs:282-330`): one +-1 impulse per cell of ceil(rate / density) samples.
+            GpuVelvet, NoiseKind::Velvet);
+impl GpuWhiteUniform { pub fn std_dev(&self) -> f32 { (1.0f32 / 3.0).sqrt() } }
+impl GpuWhiteTriangular { pub fn std_dev(&self) -> f32 { 2.0 / 6.0f32.sqrt() } }
+impl GpuWhiteGaussian {
+    pub fn mean(&self) -> f32 { 0.0 }
+    pub fn std_dev(&self) -> f32 { 0.6 }
+}
+impl GpuVelvet {
+    /// `Velvet::new_with_density(rate, density, rng)` (`noise.rs:282`): `density` impulses a second.
+    pub fn new_with_density(sample_rate: SampleRate, density: std::num::NonZeroU32, seed: u64) -> Self {
+        GpuVelvet(GpuNoise::with_seed(NoiseKind::Velvet, sample_rate, seed, density.get()))
+    }
+}
