@@ -42,7 +42,7 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "rh_common.h"), os.path.join(CSRC, "rh_scan_common.h"), os.path.join(CSRC, "rh_pipeline_internal.h"), os.path.join(CSRC, "rh_pipeline_dev.h"), os.path.join(CSRC, "rh_generators.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(HERE, "..", "include", "rodio_hip.h")]
+    headers = [os.path.join(CSRC, "rh_common.h"), os.path.join(CSRC, "rh_lanes.h"), os.path.join(CSRC, "rh_scan_common.h"), os.path.join(CSRC, "rh_pipeline_internal.h"), os.path.join(CSRC, "rh_pipeline_dev.h"), os.path.join(CSRC, "rh_generators.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(HERE, "..", "include", "rodio_hip.h")]
     cc = hipcc()
     jobs = []
     objs = []

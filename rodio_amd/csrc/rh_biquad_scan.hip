@@ -64,18 +64,12 @@ struct BqArgs {
     float BL[4];              // B^L
 };
 
-template <class MP>  // (a pointer to four floats in any address space: the matrices of the argument block are read from the constant one)
-__device__ __forceinline__ void mat_acc(MP M, float x1, float x2, float &y1, float &y2) {
-    y1 = fma_(M[0], x1, fma_(M[1], x2, y1));
-    y2 = fma_(M[2], x1, fma_(M[3], x2, y2));
-}
-
 // Inclusive wave64 scan of 2-vectors under P_l = sum_{k<=l} B^(R*(l-k)) p_k (the fused kernel's, rh_pipeline.hip).
 template <class SM>
 __device__ __forceinline__ void scan_mat(float &P0, float &P1, SM &sm, const float *b15, const float *b31) {
 #define RH_STEP(K, N)                                                                          \
     {                                                                                          \
-        const float q0 = dpp0<kRowShr + N, 0xf>(P0), q1 = dpp0<kRowShr + N, 0xf>(P1);          \
+        const float q0 = dpp0<kDppRowShr + N, 0xf>(P0), q1 = dpp0<kDppRowShr + N, 0xf>(P1);    \
         mat_acc(sm[K], q0, q1, P0, P1);                                                        \
     }
     RH_STEP(0, 1)
@@ -84,11 +78,11 @@ __device__ __forceinline__ void scan_mat(float &P0, float &P1, SM &sm, const flo
     RH_STEP(3, 8)
 #undef RH_STEP
     {
-        const float q0 = dpp0<kBcast15, 0xa>(P0), q1 = dpp0<kBcast15, 0xa>(P1);
+        const float q0 = dpp0<kDppBcast15, 0xa>(P0), q1 = dpp0<kDppBcast15, 0xa>(P1);
         mat_acc(b15, q0, q1, P0, P1);
     }
     {
-        const float q0 = dpp0<kBcast31, 0xc>(P0), q1 = dpp0<kBcast31, 0xc>(P1);
+        const float q0 = dpp0<kDppBcast31, 0xc>(P0), q1 = dpp0<kDppBcast31, 0xc>(P1);
         mat_acc(b31, q0, q1, P0, P1);
     }
 }
@@ -212,8 +206,8 @@ __device__ __forceinline__ void bq_tile(BqArgsC kargs, v4f *lds, const v4f *halo
 #ifndef RH_BQ_NO_ARITH
             scan_mat(P[c][0], P[c][1], a.scanM, b15, b31);
 #endif
-            Q[c][0] = dpp0<kWaveShr1, 0xf>(P[c][0]);  // exclusive: lane 0 gets 0
-            Q[c][1] = dpp0<kWaveShr1, 0xf>(P[c][1]);
+            Q[c][0] = dpp0<kDppWaveShr1, 0xf>(P[c][0]);  // exclusive: lane 0 gets 0
+            Q[c][1] = dpp0<kDppWaveShr1, 0xf>(P[c][1]);
             if (lane == 63) xZ[wave][2 * c] = P[c][0], xZ[wave][2 * c + 1] = P[c][1];
         }
     }

@@ -120,7 +120,7 @@ __device__ __forceinline__ float gain_computer(float sample, const GainK &k) {
 __device__ __forceinline__ void scan_maxaff(float &A, float &B, const float (&cs)[4], float c15, float c31) {
 #define RH_STEP(K, N)                                                      \
     {                                                                      \
-        const float a1 = dpp0<kRowShr + N, 0xf>(A), b1 = dpp0<kRowShr + N, 0xf>(B); \
+        const float a1 = dpp0<kDppRowShr + N, 0xf>(A), b1 = dpp0<kDppRowShr + N, 0xf>(B); \
         A = fmaxf(A, fma_(cs[K], a1, B));                                  \
         B = fma_(cs[K], b1, B);                                            \
     }
@@ -130,24 +130,24 @@ __device__ __forceinline__ void scan_maxaff(float &A, float &B, const float (&cs
     RH_STEP(3, 8)
 #undef RH_STEP
     {
-        const float a1 = dpp0<kBcast15, 0xa>(A), b1 = dpp0<kBcast15, 0xa>(B);
+        const float a1 = dpp0<kDppBcast15, 0xa>(A), b1 = dpp0<kDppBcast15, 0xa>(B);
         A = fmaxf(A, fma_(c15, a1, B));
         B = fma_(c15, b1, B);
     }
     {
-        const float a1 = dpp0<kBcast31, 0xc>(A), b1 = dpp0<kBcast31, 0xc>(B);
+        const float a1 = dpp0<kDppBcast31, 0xc>(A), b1 = dpp0<kDppBcast31, 0xc>(B);
         A = fmaxf(A, fma_(c31, a1, B));
         B = fma_(c31, b1, B);
     }
 }
 // Inclusive wave64 scan of a linear 1-pole: V_l = sum_{k<=l} c^(R*(l-k)) v_k.
 __device__ __forceinline__ void scan_lin(float &V, const float (&cs)[4], float c15, float c31) {
-    V = fma_(cs[0], dpp0<kRowShr + 1, 0xf>(V), V);
-    V = fma_(cs[1], dpp0<kRowShr + 2, 0xf>(V), V);
-    V = fma_(cs[2], dpp0<kRowShr + 4, 0xf>(V), V);
-    V = fma_(cs[3], dpp0<kRowShr + 8, 0xf>(V), V);
-    V = fma_(c15, dpp0<kBcast15, 0xa>(V), V);
-    V = fma_(c31, dpp0<kBcast31, 0xc>(V), V);
+    V = fma_(cs[0], dpp0<kDppRowShr + 1, 0xf>(V), V);
+    V = fma_(cs[1], dpp0<kDppRowShr + 2, 0xf>(V), V);
+    V = fma_(cs[2], dpp0<kDppRowShr + 4, 0xf>(V), V);
+    V = fma_(cs[3], dpp0<kDppRowShr + 8, 0xf>(V), V);
+    V = fma_(c15, dpp0<kDppBcast15, 0xa>(V), V);
+    V = fma_(c31, dpp0<kDppBcast31, 0xc>(V), V);
 }
 // ---- hand-off words ---------------------------------------------------------------------------------------------------
 // A tile publishes its aggregates / end states as plain f32 words in a table that is filled with 0xFF bytes on the stream
@@ -344,22 +344,22 @@ __device__ __forceinline__ void scan_maxaff_v(T &A, T &B, const float (&cs)[4], 
         A = vmax(A, vfma(splat<T>(CS), a1, B));                            \
         B = vfma(splat<T>(CS), b1, B);                                     \
     }
-    RH_STEP(cs[0], kRowShr + 1, 0xf)
-    RH_STEP(cs[1], kRowShr + 2, 0xf)
-    RH_STEP(cs[2], kRowShr + 4, 0xf)
-    RH_STEP(cs[3], kRowShr + 8, 0xf)
-    RH_STEP(c15, kBcast15, 0xa)
-    RH_STEP(c31, kBcast31, 0xc)
+    RH_STEP(cs[0], kDppRowShr + 1, 0xf)
+    RH_STEP(cs[1], kDppRowShr + 2, 0xf)
+    RH_STEP(cs[2], kDppRowShr + 4, 0xf)
+    RH_STEP(cs[3], kDppRowShr + 8, 0xf)
+    RH_STEP(c15, kDppBcast15, 0xa)
+    RH_STEP(c31, kDppBcast31, 0xc)
 #undef RH_STEP
 }
 template <class T>
 __device__ __forceinline__ void scan_lin_v(T &V, const float (&cs)[4], float c15, float c31) {
-    V = vfma(splat<T>(cs[0]), vdpp<kRowShr + 1, 0xf>(V), V);
-    V = vfma(splat<T>(cs[1]), vdpp<kRowShr + 2, 0xf>(V), V);
-    V = vfma(splat<T>(cs[2]), vdpp<kRowShr + 4, 0xf>(V), V);
-    V = vfma(splat<T>(cs[3]), vdpp<kRowShr + 8, 0xf>(V), V);
-    V = vfma(splat<T>(c15), vdpp<kBcast15, 0xa>(V), V);
-    V = vfma(splat<T>(c31), vdpp<kBcast31, 0xc>(V), V);
+    V = vfma(splat<T>(cs[0]), vdpp<kDppRowShr + 1, 0xf>(V), V);
+    V = vfma(splat<T>(cs[1]), vdpp<kDppRowShr + 2, 0xf>(V), V);
+    V = vfma(splat<T>(cs[2]), vdpp<kDppRowShr + 4, 0xf>(V), V);
+    V = vfma(splat<T>(cs[3]), vdpp<kDppRowShr + 8, 0xf>(V), V);
+    V = vfma(splat<T>(c15), vdpp<kDppBcast15, 0xa>(V), V);
+    V = vfma(splat<T>(c31), vdpp<kDppBcast31, 0xc>(V), V);
 }
 
 // One wave's share (L = 64*R frames) of a workgroup tile (NW waves, LW = NW*L frames of one stream).
@@ -520,8 +520,8 @@ __device__ __forceinline__ void limit_tile(ArgsC kargs, v4f *lds, float (*xI)[2 
 #pragma unroll
     for (int p = 0; p < N; ++p) {
         scan_maxaff_v<T>(A[p], B[p], rscan, r15, r31);
-        Ax[p] = vdpp<kWaveShr1, 0xf>(A[p]);
-        Bx[p] = vdpp<kWaveShr1, 0xf>(B[p]);
+        Ax[p] = vdpp<kDppWaveShr1, 0xf>(A[p]);
+        Bx[p] = vdpp<kDppWaveShr1, 0xf>(B[p]);
     }
     if (lane == 63) {
 #pragma unroll
@@ -629,7 +629,7 @@ __device__ __forceinline__ void limit_tile(ArgsC kargs, v4f *lds, float (*xI)[2 
     for (int p = 0; p < N; ++p) {
         T Pi = Pz[p];
         scan_lin_v<T>(Pi, ascan, a15, a31);
-        Px[p] = vdpp<kWaveShr1, 0xf>(Pi);
+        Px[p] = vdpp<kDppWaveShr1, 0xf>(Pi);
         if (lane == 63) {
 #pragma unroll
             for (int w = 0; w < W; ++w) xP[wave][p * W + w] = comp(Pi, w);

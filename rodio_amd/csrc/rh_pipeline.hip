@@ -422,6 +422,7 @@ __global__ __launch_bounds__(64, (R <= 4 ? (KV <= 5 ? 5 : 4) : R <= 6 ? 3 : R <=
         for (int q = 0; q < 2 * C; ++q) P[q] = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) mat_acc(p.u.Tm, CH::get(E1, c), CH::get(E2, c), P[2 * c], P[2 * c + 1]);
+        // (scan_states of rh_pipeline_dev.h, written out: as a call, 20 instances of this kernel compile to other code -- profiles/refactor_scan_helpers.txt)
 #define RH_SCAN_STEP(K, N)                                                                          \
     {                                                                                               \
         float sq[2 * C];                                                                            \
@@ -504,14 +505,7 @@ __global__ __launch_bounds__(64, (R <= 4 ? (KV <= 5 ? 5 : 4) : R <= 6 ? 3 : R <=
 #pragma unroll
                 for (int q = 0; q < 2 * C; ++q) c[q] = __builtin_nanf("");
             }
-#pragma unroll
-            for (int q = 0; q < 2 * C; ++q) {  // sum over lanes 0..31 -> uniform
-                c[q] += dpp0<kDppRowShr + 1, 0xf>(c[q]);
-                c[q] += dpp0<kDppRowShr + 2, 0xf>(c[q]);
-                c[q] += dpp0<kDppRowShr + 4, 0xf>(c[q]);
-                c[q] += dpp0<kDppRowShr + 8, 0xf>(c[q]);
-                c[q] = readlane_f(c[q], 15) + readlane_f(c[q], 31);
-            }
+            half_wave_sum(c);  // sum over lanes 0..31 -> uniform
         }
         if (p.st_mode && tile < p.J) {  // the stream's state at the block start still reaches this tile: + B^(L*tile) * W_in
             const float *M = tb->lookM[tile];
@@ -780,17 +774,6 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
         return d;
     };
 
-    // Sum of the lanes' carry shares (lanes < 32 hold them), as a wave-uniform value.
-    auto reduce_carry = [&](float (&c)[4]) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            c[q] += dpp0<kDppRowShr + 1, 0xf>(c[q]);
-            c[q] += dpp0<kDppRowShr + 2, 0xf>(c[q]);
-            c[q] += dpp0<kDppRowShr + 4, 0xf>(c[q]);
-            c[q] += dpp0<kDppRowShr + 8, 0xf>(c[q]);
-            c[q] = readlane_f(c[q], 15) + readlane_f(c[q], 31);
-        }
-    };
     // Poll one 32-byte aggregate per lane until it carries this launch's epoch (ordinary agent-scope
     // loads: hipcc waits for them, which also drains the DMA ring -- this is the slow path).
     auto poll_sets = [&](const unsigned long long *gp, bool want, unsigned long long (&gv)[4], bool &ok) {
@@ -997,30 +980,7 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
                 float P[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int c = 0; c < C; ++c) mat_acc(p.u.Tm, CH::get(w1, c) * g, CH::get(w2, c) * g, P[2 * c], P[2 * c + 1]);
-#define RH_SCAN_STEP(K, N)                                                                          \
-    {                                                                                               \
-        const float q0 = dpp0<kDppRowShr + N, 0xf>(P[0]), q1 = dpp0<kDppRowShr + N, 0xf>(P[1]);     \
-        const float q2 = dpp0<kDppRowShr + N, 0xf>(P[2]), q3 = dpp0<kDppRowShr + N, 0xf>(P[3]);     \
-        mat_acc(p.u.scanM[K], q0, q1, P[0], P[1]);                                                  \
-        mat_acc(p.u.scanM[K], q2, q3, P[2], P[3]);                                                  \
-    }
-                RH_SCAN_STEP(0, 1)
-                RH_SCAN_STEP(1, 2)
-                RH_SCAN_STEP(2, 4)
-                RH_SCAN_STEP(3, 8)
-#undef RH_SCAN_STEP
-                {  // rows 1 and 3 take the inclusive prefix of the row before them
-                    const float q0 = dpp0<kDppBcast15, 0xa>(P[0]), q1 = dpp0<kDppBcast15, 0xa>(P[1]);
-                    const float q2 = dpp0<kDppBcast15, 0xa>(P[2]), q3 = dpp0<kDppBcast15, 0xa>(P[3]);
-                    mat_acc(b15, q0, q1, P[0], P[1]);
-                    mat_acc(b15, q2, q3, P[2], P[3]);
-                }
-                {  // rows 2 and 3 take the inclusive prefix of lanes 0..31
-                    const float q0 = dpp0<kDppBcast31, 0xc>(P[0]), q1 = dpp0<kDppBcast31, 0xc>(P[1]);
-                    const float q2 = dpp0<kDppBcast31, 0xc>(P[2]), q3 = dpp0<kDppBcast31, 0xc>(P[3]);
-                    mat_acc(b31, q0, q1, P[0], P[1]);
-                    mat_acc(b31, q2, q3, P[2], P[3]);
-                }
+                scan_states(P, ScanStepsArgs{p.u}, b15, b31);  // (the step matrices from the argument block)
                 // the tile aggregate (lane 63's inclusive prefix) waits in LDS for the group's publication
                 if (lane == 63) *(lds_f4 *)(lds + kPubBase + (s & 7) * 16) = v4f{P[0], P[1], P[2], P[3]};
                 pubmask |= 1u << (s & 7);
@@ -1047,7 +1007,7 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
                             mat_acc(kM, __uint_as_float((uint32_t)gv[0]), __uint_as_float((uint32_t)gv[1]), c[0], c[1]);
                             mat_acc(kM, __uint_as_float((uint32_t)gv[2]), __uint_as_float((uint32_t)gv[3]), c[2], c[3]);
                         }
-                        reduce_carry(c);
+                        half_wave_sum(c);  // sum over lanes 0..31 -> uniform
                     }
                     mat_acc(lM, c[0], c[1], Qnew[0], Qnew[1]);
                     mat_acc(lM, c[2], c[3], Qnew[2], Qnew[3]);
@@ -1113,30 +1073,7 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
         float P[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < C; ++c) mat_acc(p.u.Tm, CH::get(E1s, c), CH::get(E2s, c), P[2 * c], P[2 * c + 1]);
-#define RH_SCAN_STEP(K, N)                                                                          \
-    {                                                                                               \
-        const float q0 = dpp0<kDppRowShr + N, 0xf>(P[0]), q1 = dpp0<kDppRowShr + N, 0xf>(P[1]);     \
-        const float q2 = dpp0<kDppRowShr + N, 0xf>(P[2]), q3 = dpp0<kDppRowShr + N, 0xf>(P[3]);     \
-        mat_acc(p.u.scanM[K], q0, q1, P[0], P[1]);                                                  \
-        mat_acc(p.u.scanM[K], q2, q3, P[2], P[3]);                                                  \
-    }
-        RH_SCAN_STEP(0, 1)
-        RH_SCAN_STEP(1, 2)
-        RH_SCAN_STEP(2, 4)
-        RH_SCAN_STEP(3, 8)
-#undef RH_SCAN_STEP
-        {
-            const float q0 = dpp0<kDppBcast15, 0xa>(P[0]), q1 = dpp0<kDppBcast15, 0xa>(P[1]);
-            const float q2 = dpp0<kDppBcast15, 0xa>(P[2]), q3 = dpp0<kDppBcast15, 0xa>(P[3]);
-            mat_acc(b15, q0, q1, P[0], P[1]);
-            mat_acc(b15, q2, q3, P[2], P[3]);
-        }
-        {
-            const float q0 = dpp0<kDppBcast31, 0xc>(P[0]), q1 = dpp0<kDppBcast31, 0xc>(P[1]);
-            const float q2 = dpp0<kDppBcast31, 0xc>(P[2]), q3 = dpp0<kDppBcast31, 0xc>(P[3]);
-            mat_acc(b31, q0, q1, P[0], P[1]);
-            mat_acc(b31, q2, q3, P[2], P[3]);
-        }
+        scan_states(P, ScanStepsArgs{p.u}, b15, b31);  // (the step matrices from the argument block)
         unsigned long long *const sum_row = p.gran + (uint64_t)S * ncol * 4;
         {
             const float e0 = readlane_f(P[0], 63), e1 = readlane_f(P[1], 63);
@@ -1164,7 +1101,7 @@ __global__ __launch_bounds__(64, (R <= 8 && KV <= 5 ? 3 : 2)) void k_rlm_wave(co
     }
     if (FILT) {  // the merged homogeneous response: start state = Qacc + B^(R*lane) * (summed tile carries)
         if (dead) Cacc[0] = Cacc[1] = Cacc[2] = Cacc[3] = __builtin_nanf("");  // a carry never arrived: poison the tile (the status word fails the call)
-        reduce_carry(Cacc);
+        half_wave_sum(Cacc);  // sum over lanes 0..31 -> uniform
         mat_acc(lM, Cacc[0], Cacc[1], Qacc[0], Qacc[1]);
         mat_acc(lM, Cacc[2], Cacc[3], Qacc[2], Qacc[3]);
 #pragma unroll
@@ -1756,50 +1693,11 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
     float own[2 * C];
 #pragma unroll
     for (int k = 0; k < 2 * C; ++k) own[k] = Pq[k];
-#define RH_CSCAN(K, N)                                                                             \
-    {                                                                                              \
-        float sq[2 * C];                                                                           \
-        _Pragma("unroll") for (int k = 0; k < 2 * C; ++k) sq[k] = dpp0<kDppRowShr + N, 0xf>(Pq[k]); \
-        const float sM[4] = {readlane_f(U, 9 + 4 * K), readlane_f(U, 10 + 4 * K), readlane_f(U, 11 + 4 * K), readlane_f(U, 12 + 4 * K)}; \
-        _Pragma("unroll") for (int ch = 0; ch < C; ++ch) mat_acc(sM, sq[2 * ch], sq[2 * ch + 1], Pq[2 * ch], Pq[2 * ch + 1]); \
-    }
-    RH_CSCAN(0, 1)
-    RH_CSCAN(1, 2)
-    RH_CSCAN(2, 4)
-    RH_CSCAN(3, 8)
-#undef RH_CSCAN
-    {
-        float sq[2 * C];
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) sq[k] = dpp0<kDppBcast15, 0xa>(Pq[k]);
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) mat_acc(b15, sq[2 * ch], sq[2 * ch + 1], Pq[2 * ch], Pq[2 * ch + 1]);
-    }
-    {
-        float sq[2 * C];
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) sq[k] = dpp0<kDppBcast31, 0xc>(Pq[k]);
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) mat_acc(b31, sq[2 * ch], sq[2 * ch + 1], Pq[2 * ch], Pq[2 * ch + 1]);
-    }
+    scan_states(Pq, ScanStepsLanes{U}, b15, b31);  // (the step matrices from U)
     {  // the tile aggregate: the short last run on top of the inclusive prefix of the lane before it
         const uint32_t n_t = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_t_v);
-        const int nl = (int)((n_t + R - 1) / R);  // lanes with frames (uniform)
         float A[2 * C];
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) A[k] = 0.f;
-        if (nl >= 1) {
-#pragma unroll
-            for (int k = 0; k < 2 * C; ++k) A[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(own[k]), nl - 1));
-        }
-        if (nl >= 2) {
-            const float M[4] = {readfirstlane_f(pwv[0]), readfirstlane_f(pwv[1]), readfirstlane_f(pwv[2]), readfirstlane_f(pwv[3])};  // B^v
-            float xp[2 * C];
-#pragma unroll
-            for (int k = 0; k < 2 * C; ++k) xp[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Pq[k]), nl - 2));
-#pragma unroll
-            for (int ch = 0; ch < C; ++ch) mat_acc(M, xp[2 * ch], xp[2 * ch + 1], A[2 * ch], A[2 * ch + 1]);
-        }
+        tile_aggregate(own, Pq, pwv, (int)((n_t + R - 1) / R), A);
         if (lane < 2 * C) {
             float ev = A[0];
 #pragma unroll
@@ -1847,7 +1745,7 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
             for (int ch = 0; ch < C; ++ch) mat_acc(kM, __uint_as_float((uint32_t)gv[2 * ch]), __uint_as_float((uint32_t)gv[2 * ch + 1]), c[2 * ch], c[2 * ch + 1]);
         }
 #pragma unroll
-        for (int k = 0; k < 2 * C; ++k) {  // sum over lanes 0..31 -> uniform
+        for (int k = 0; k < 2 * C; ++k) {  // sum over lanes 0..31 -> uniform (half_wave_sum, written out: as a call the stereo kernel grows by 9 instructions)
             c[k] += dpp0<kDppRowShr + 1, 0xf>(c[k]);
             c[k] += dpp0<kDppRowShr + 2, 0xf>(c[k]);
             c[k] += dpp0<kDppRowShr + 4, 0xf>(c[k]);
@@ -1862,38 +1760,13 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
     RH_CPH(3)  // look-back
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) mat_acc(lM, c[2 * ch], c[2 * ch + 1], Q[2 * ch], Q[2 * ch + 1]);  // start state of the lane's run = Q + B^(R*lane) * carry
-    // A lane's run is R * FB contiguous bytes, so a store of one frame per lane touches 64 different lines.  The runs go through
-    // the (now idle) ring stages -- rows padded by one frame -- and leave as whole lines: lane l stores frame k * 64 + l of the tile.
-    constexpr uint32_t kRow = (R + 1) * FB;
-    {
-        lds_u8 *row = lds + (uint32_t)lane * kRow;
+    // out[r] + the homogeneous correction, through the (now idle) ring stages
+    tile_store<R, C>(lds, lane, [&] { return (uint32_t)__builtin_amdgcn_readfirstlane((int)n_t_v); }, [&] { return (float *)(uintptr_t)a_out; }, [&](int r) {
+        V y;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            V y;
-#pragma unroll
-            for (int ch = 0; ch < C; ++ch) CH::set(y, ch, fma_(readlane_f(U, 25 + 2 * r), Q[2 * ch], fma_(readlane_f(U, 26 + 2 * r), Q[2 * ch + 1], CH::get(out[r], ch))));
-            if (C == 2) *(lds_f2 *)(row + r * FB) = v2f{CH::get(y, 0), CH::get(y, C - 1)};
-            else *(RH_LDS float *)(row + r * FB) = CH::get(y, 0);
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    {
-        const uint32_t n_t = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_t_v);
-        float *ot = (float *)(uintptr_t)a_out;  // this lane's frame of every group of 64
-        for (uint32_t f0 = 0; f0 < n_t; f0 += 64) {
-            const uint32_t f = f0 + (uint32_t)lane;
-            if (f < n_t) {
-                const lds_u8 *src2 = lds + (f / R) * kRow + (f % R) * FB;
-                if (C == 2) {
-                    const v2f a = *(const lds_f2 *)src2;
-                    *reinterpret_cast<float2 *>(ot + (uint64_t)f0 * 2) = make_float2(a.x, a.y);
-                } else {
-                    ot[f0] = *(const RH_LDS float *)src2;
-                }
-            }
-        }
-    }
+        for (int ch = 0; ch < C; ++ch) CH::set(y, ch, fma_(readlane_f(U, 25 + 2 * r), Q[2 * ch], fma_(readlane_f(U, 26 + 2 * r), Q[2 * ch + 1], CH::get(out[r], ch))));
+        return y;
+    });
     RH_CPH(4)  // correction + stores (issue)
 }
 template <int R, int C, int KV>
@@ -2257,6 +2130,8 @@ __global__ __launch_bounds__(128, 2) void k_rlm_chunk_classes(const ChunkMulti m
         float own[2 * C];
 #pragma unroll
         for (int i = 0; i < 2 * C; ++i) own[i] = Pq[i];
+        // (scan_states, tile_aggregate and tile_store of rh_pipeline_dev.h, written out in this kernel: as calls they cost it registers and scalar spills --
+        // profiles/refactor_scan_helpers.txt)
 #define RH_CSCAN(K, N)                                                                             \
     {                                                                                              \
         float sq[2 * C];                                                                           \
@@ -2344,14 +2219,7 @@ __global__ __launch_bounds__(128, 2) void k_rlm_chunk_classes(const ChunkMulti m
 #pragma unroll
                 for (int ch = 0; ch < C; ++ch) mat_acc(kM, __uint_as_float((uint32_t)gv[2 * ch]), __uint_as_float((uint32_t)gv[2 * ch + 1]), c[2 * ch], c[2 * ch + 1]);
             }
-#pragma unroll
-            for (int i = 0; i < 2 * C; ++i) {  // sum over lanes 0..31 -> uniform
-                c[i] += dpp0<kDppRowShr + 1, 0xf>(c[i]);
-                c[i] += dpp0<kDppRowShr + 2, 0xf>(c[i]);
-                c[i] += dpp0<kDppRowShr + 4, 0xf>(c[i]);
-                c[i] += dpp0<kDppRowShr + 8, 0xf>(c[i]);
-                c[i] = readlane_f(c[i], 15) + readlane_f(c[i], 31);
-            }
+            half_wave_sum(c);  // sum over lanes 0..31 -> uniform
         }
         if (dead) {
 #pragma unroll
@@ -2521,30 +2389,7 @@ __device__ __forceinline__ void rag_run_pairs(const Params &p, unsigned long lon
         float P[4] = {0.f, 0.f, 0.f, 0.f};  // (mono: the second channel's words stay zero and travel as zeros, as in k_rlm_wave)
         mat_acc(p.u.Tm, CH::get(w1, 0) * g, CH::get(w2, 0) * g, P[0], P[1]);
         if (C == 2) mat_acc(p.u.Tm, CH::get(w1, C - 1) * g, CH::get(w2, C - 1) * g, P[2], P[3]);
-#define RH_SCAN_STEP(K, N)                                                                          \
-    {                                                                                               \
-        const float q0 = dpp0<kDppRowShr + N, 0xf>(P[0]), q1 = dpp0<kDppRowShr + N, 0xf>(P[1]);     \
-        const float q2 = dpp0<kDppRowShr + N, 0xf>(P[2]), q3 = dpp0<kDppRowShr + N, 0xf>(P[3]);     \
-        mat_acc(p.u.scanM[K], q0, q1, P[0], P[1]);                                                  \
-        mat_acc(p.u.scanM[K], q2, q3, P[2], P[3]);                                                  \
-    }
-        RH_SCAN_STEP(0, 1)
-        RH_SCAN_STEP(1, 2)
-        RH_SCAN_STEP(2, 4)
-        RH_SCAN_STEP(3, 8)
-#undef RH_SCAN_STEP
-        {
-            const float q0 = dpp0<kDppBcast15, 0xa>(P[0]), q1 = dpp0<kDppBcast15, 0xa>(P[1]);
-            const float q2 = dpp0<kDppBcast15, 0xa>(P[2]), q3 = dpp0<kDppBcast15, 0xa>(P[3]);
-            mat_acc(b15, q0, q1, P[0], P[1]);
-            mat_acc(b15, q2, q3, P[2], P[3]);
-        }
-        {
-            const float q0 = dpp0<kDppBcast31, 0xc>(P[0]), q1 = dpp0<kDppBcast31, 0xc>(P[1]);
-            const float q2 = dpp0<kDppBcast31, 0xc>(P[2]), q3 = dpp0<kDppBcast31, 0xc>(P[3]);
-            mat_acc(b31, q0, q1, P[0], P[1]);
-            mat_acc(b31, q2, q3, P[2], P[3]);
-        }
+        scan_states(P, ScanStepsArgs{p.u}, b15, b31);  // (the step matrices from the argument block)
         unsigned long long *const row = rows + (uint64_t)s * ncol * 4;
         {  // this source's own aggregate for the tile (a later tile of it polls for it)
             const float e0 = readlane_f(P[0], 63), e1 = readlane_f(P[1], 63);
@@ -2592,14 +2437,7 @@ __device__ __forceinline__ void rag_run_pairs(const Params &p, unsigned long lon
                 mat_acc(kM, __uint_as_float((uint32_t)gv[2]), __uint_as_float((uint32_t)gv[3]), c[2], c[3]);
             }
             if (dead) c[0] = c[1] = c[2] = c[3] = __builtin_nanf("");  // poison: see k_rlm_fast
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {  // sum over lanes 0..31 -> uniform
-                c[q] += dpp0<kDppRowShr + 1, 0xf>(c[q]);
-                c[q] += dpp0<kDppRowShr + 2, 0xf>(c[q]);
-                c[q] += dpp0<kDppRowShr + 4, 0xf>(c[q]);
-                c[q] += dpp0<kDppRowShr + 8, 0xf>(c[q]);
-                c[q] = readlane_f(c[q], 15) + readlane_f(c[q], 31);
-            }
+            half_wave_sum(c);  // sum over lanes 0..31 -> uniform
         }
         mat_acc(lM, c[0], c[1], Q[0], Q[1]);
         mat_acc(lM, c[2], c[3], Q[2], Q[3]);

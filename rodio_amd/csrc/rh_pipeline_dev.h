@@ -1,6 +1,6 @@
 // rh_pipeline_dev.h -- device-side helpers the kernels of the fused path share (rh_pipeline.hip: k_rlm_fast / k_rlm_wave / k_rlm_chunk /
-// k_mix_*; rh_pipeline_sblk.hip: k_rlm_sblk): the converter's cursor, the 2x2 products, DPP moves, the hand-counted LDS-DMA pipeline, the
-// channel-count helpers.  Not part of the C ABI.  Everything sits in an unnamed namespace: every unit gets its own copies.
+// k_mix_*; rh_pipeline_sblk.hip: k_rlm_sblk): the converter's cursor, the lane primitives (rh_lanes.h), the hand-counted LDS-DMA pipeline, the
+// channel-count helpers, the state scan / tile aggregate / carry sum / tile store behind the source loops.  Not part of the C ABI.  Everything sits in an unnamed namespace: every unit gets its own copies.
 #pragma once
 #include "rh_pipeline_internal.h"
 
@@ -53,32 +53,12 @@ __device__ __forceinline__ void cursor_resolve(const Cursor &c, const Params &p,
     i = c.k * p.chunk_in + il;
 }
 
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+#include "rh_lanes.h"  // fma_, mat_acc, dpp0 and its control words, readlane_f / readfirstlane_f
 
 // t / T of math.rs:25: rh::div_lerp (rh_common.h) -- three instructions and a select where that is the IEEE quotient (rcpT = rh::lerp_rcp(T): this
 // T checked exhaustively; zeros and infinities handled), the IEEE sequence for a T that failed the check.  Until round 6's last session this was
 // the bare three instructions: +0 for t = -0 (every frame that lands on a tap), NaN for t = Inf.  Nonzero |t| < 2^-120 may still be an ulp off.
 __device__ __forceinline__ float div_T(float t, float Tf, float rcpT) { return rh::div_lerp(t, Tf, rcpT); }
-
-// y += M * x for a row-major 2x2
-__device__ __forceinline__ void mat_acc(const float *M, float x1, float x2, float &y1, float &y2) {
-    y1 = fma_(M[0], x1, fma_(M[1], x2, y1));
-    y2 = fma_(M[2], x1, fma_(M[3], x2, y2));
-}
-
-// Cross-lane moves on the VALU data path (DPP), no LDS round trip.  Lanes whose source is out of
-// range, or whose row is masked off, read 0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp0(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
-// v_readlane / v_readfirstlane of a float (the builtins take int: pass the bits, not the value)
-__device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ float readfirstlane_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-constexpr int kDppRowShr = 0x110;    // row_shr:n  = 0x110 + n
-constexpr int kDppWaveShr1 = 0x138;  // wave_shr:1
-constexpr int kDppBcast15 = 0x142;   // lane 15 of each row -> the next row
-constexpr int kDppBcast31 = 0x143;   // lane 31 -> rows 2 and 3
 
 #define RH_LDS __attribute__((address_space(3)))
 typedef RH_LDS unsigned char lds_u8;
@@ -262,5 +242,117 @@ __device__ __forceinline__ v2f vmul_s(v2f a, float s) { return v2f{a.x * s, a.y 
 __device__ __forceinline__ float vmul_s(float a, float s) { return a * s; }
 __device__ __forceinline__ v2f vsel(bool c, v2f a, v2f b) { return v2f{c ? a.x : b.x, c ? a.y : b.y}; }
 __device__ __forceinline__ float vsel(bool c, float a, float b) { return c ? a : b; }
+
+// ---- what the fused kernels do with the lanes' run-end states behind their source loops: scan, tile aggregate, carry sum, the tile's way out ----
+// A state is two floats per channel in the scan basis: P[2c], P[2c + 1] (N = 2 C floats; k_rlm_wave and the ragged pairs keep N = 4 for mono
+// too, the second channel's words travel as zeros).  These helpers are held to one rule: a kernel that calls one compiles to the instructions it
+// had with the block written out (profiles/refactor_scan_helpers.txt).  That is why values that a kernel always worked out late arrive as
+// callables (the step matrix behind the DPP moves, the frame count and the destination behind the LDS round trip), and why k_rlm_fast and
+// k_rlm_chunk_classes still spell their scan, and every kernel its publication and its look-back poll: as calls they compiled differently.
+//
+// The wave64 inclusive scan P_l = sum_{k <= l} B^(R (l - k)) p_k: four row_shr steps with B^(R 2^K) inside the rows of 16, then rows 1 and 3 take
+// the inclusive prefix of the row before them (bcast15, b15 = B^(R ((l & 15) + 1))), then rows 2 and 3 that of lanes 0..31 (bcast31, b31).  The
+// step matrices come from `steps(K)`: ScanStepsArgs (the kernel's argument block: scalar loads) or ScanStepsLanes (floats 9 + 4 K .. of the
+// Uniforms, one per lane of U: no memory access behind a source loop).
+struct Mat2 {
+    float m[4];
+    __device__ __forceinline__ float operator[](int i) const { return m[i]; }
+};
+struct ScanStepsArgs {
+    const Uniforms &u;
+    __device__ __forceinline__ const float *operator()(int K) const { return u.scanM[K]; }
+};
+struct ScanStepsLanes {
+    float U;
+    __device__ __forceinline__ Mat2 operator()(int K) const { return Mat2{{readlane_f(U, 9 + 4 * K), readlane_f(U, 10 + 4 * K), readlane_f(U, 11 + 4 * K), readlane_f(U, 12 + 4 * K)}}; }
+};
+struct ScanStepRegs {  // (b15 / b31: one matrix, in this lane's registers)
+    const float (&m)[4];
+    __device__ __forceinline__ const float *operator()(int) const { return m; }
+};
+// one step: the states CTRL away, times the step's matrix (asked for behind the moves), onto this lane's
+template <int CTRL, int ROW_MASK, int N, class STEPS>
+__device__ __forceinline__ void scan_step(float (&P)[N], const STEPS &steps, const int K) {
+    float sq[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) sq[k] = dpp0<CTRL, ROW_MASK>(P[k]);
+    const auto M = steps(K);
+#pragma unroll
+    for (int ch = 0; ch < N / 2; ++ch) mat_acc(M, sq[2 * ch], sq[2 * ch + 1], P[2 * ch], P[2 * ch + 1]);
+}
+template <int N, class STEPS>
+__device__ __forceinline__ void scan_states(float (&P)[N], const STEPS steps, const float (&b15)[4], const float (&b31)[4]) {
+    scan_step<kDppRowShr + 1, 0xf>(P, steps, 0);
+    scan_step<kDppRowShr + 2, 0xf>(P, steps, 1);
+    scan_step<kDppRowShr + 4, 0xf>(P, steps, 2);
+    scan_step<kDppRowShr + 8, 0xf>(P, steps, 3);
+    scan_step<kDppBcast15, 0xa>(P, ScanStepRegs{b15}, 0);  // rows 1 and 3 take the inclusive prefix of the row before them
+    scan_step<kDppBcast31, 0xc>(P, ScanStepRegs{b31}, 0);  // rows 2 and 3 take the inclusive prefix of lanes 0..31
+}
+// The aggregate of a tile whose last lane holds a SHORT run (k_rlm_chunk, k_rlm_sblk: nl lanes with frames, the last one v <= R of them): the
+// short last run on top of the inclusive prefix of the lane before it, A = own[nl - 1] + B^v * P[nl - 2].  own: the lanes' states before the
+// scan; pwv: B^v (the same in every lane).  nl uniform.
+template <int N>
+__device__ __forceinline__ void tile_aggregate(const float (&own)[N], const float (&P)[N], const float (&pwv)[4], const int nl, float (&A)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) A[k] = 0.f;
+    if (nl >= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) A[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(own[k]), nl - 1));
+    }
+    if (nl >= 2) {
+        const float M[4] = {readfirstlane_f(pwv[0]), readfirstlane_f(pwv[1]), readfirstlane_f(pwv[2]), readfirstlane_f(pwv[3])};  // B^v
+        float xp[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) xp[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(P[k]), nl - 2));
+#pragma unroll
+        for (int ch = 0; ch < N / 2; ++ch) mat_acc(M, xp[2 * ch], xp[2 * ch + 1], A[2 * ch], A[2 * ch + 1]);
+    }
+}
+// Sum over lanes 0..31 (the lanes that hold a share of the carry) -> the same value in every lane
+template <int N>
+__device__ __forceinline__ void half_wave_sum(float (&c)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        c[k] += dpp0<kDppRowShr + 1, 0xf>(c[k]);
+        c[k] += dpp0<kDppRowShr + 2, 0xf>(c[k]);
+        c[k] += dpp0<kDppRowShr + 4, 0xf>(c[k]);
+        c[k] += dpp0<kDppRowShr + 8, 0xf>(c[k]);
+        c[k] = readlane_f(c[k], 15) + readlane_f(c[k], 31);
+    }
+}
+// A tile's way out.  A lane's run is R * FB contiguous bytes, so a store of one frame per lane touches 64 different lines.  The runs go through
+// idle LDS -- rows padded by one frame -- and leave as whole lines: lane l stores frame k * 64 + l of the tile.  rows: 64 rows of (R + 1) frames; frame(r): frame r of this lane's run; count(): the tile's frames (uniform), dest(): where frame `lane`
+// of the tile goes -- both asked for behind the LDS round trip, where the kernels always worked them out.
+template <int R, int C, class COUNT, class DEST, class FRAME>
+__device__ __forceinline__ void tile_store(lds_u8 *rows, const int lane, COUNT count, DEST dest, FRAME frame) {
+    typedef Chan<C> CH;
+    constexpr uint32_t FB = CH::kFB, kRow = (R + 1) * FB;
+    {
+        lds_u8 *row = rows + (uint32_t)lane * kRow;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const typename CH::V y = frame(r);
+            if (C == 2) *(lds_f2 *)(row + r * FB) = v2f{CH::get(y, 0), CH::get(y, C - 1)};
+            else *(RH_LDS float *)(row + r * FB) = CH::get(y, 0);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t n_t = count();
+    float *ot = dest();
+    for (uint32_t f0 = 0; f0 < n_t; f0 += 64) {
+        const uint32_t f = f0 + (uint32_t)lane;
+        if (f < n_t) {
+            const lds_u8 *src2 = rows + (f / R) * kRow + (f % R) * FB;
+            if (C == 2) {
+                const v2f a = *(const lds_f2 *)src2;
+                *reinterpret_cast<float2 *>(ot + (uint64_t)f0 * 2) = make_float2(a.x, a.y);
+            } else {
+                ot[f0] = *(const RH_LDS float *)src2;
+            }
+        }
+    }
+}
 
 }  // namespace

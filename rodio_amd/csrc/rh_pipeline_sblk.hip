@@ -345,49 +345,10 @@ __global__ __launch_bounds__(64 * (kSblkWaves + 1), (NS * KV <= 8 ? 5 : 3)) void
     float own[2 * C];
 #pragma unroll
     for (int k = 0; k < 2 * C; ++k) own[k] = Pq[k];
-#define RH_SSCAN(K, N)                                                                             \
-    {                                                                                              \
-        float sq[2 * C];                                                                           \
-        _Pragma("unroll") for (int k = 0; k < 2 * C; ++k) sq[k] = dpp0<kDppRowShr + N, 0xf>(Pq[k]); \
-        const float sM[4] = {readlane_f(U, 9 + 4 * K), readlane_f(U, 10 + 4 * K), readlane_f(U, 11 + 4 * K), readlane_f(U, 12 + 4 * K)}; \
-        _Pragma("unroll") for (int ch = 0; ch < C; ++ch) mat_acc(sM, sq[2 * ch], sq[2 * ch + 1], Pq[2 * ch], Pq[2 * ch + 1]); \
-    }
-    RH_SSCAN(0, 1)
-    RH_SSCAN(1, 2)
-    RH_SSCAN(2, 4)
-    RH_SSCAN(3, 8)
-#undef RH_SSCAN
-    {
-        float sq[2 * C];
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) sq[k] = dpp0<kDppBcast15, 0xa>(Pq[k]);
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) mat_acc(b15, sq[2 * ch], sq[2 * ch + 1], Pq[2 * ch], Pq[2 * ch + 1]);
-    }
-    {
-        float sq[2 * C];
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) sq[k] = dpp0<kDppBcast31, 0xc>(Pq[k]);
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) mat_acc(b31, sq[2 * ch], sq[2 * ch + 1], Pq[2 * ch], Pq[2 * ch + 1]);
-    }
+    scan_states(Pq, ScanStepsLanes{U}, b15, b31);  // (the step matrices from U)
     float A[2 * C];  // the tile aggregate: the short last run on top of the inclusive prefix of the lane before it
     {
-        const int nl = (int)((n_t + R - 1) / R);  // lanes with frames (uniform)
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) A[k] = 0.f;
-        if (nl >= 1) {
-#pragma unroll
-            for (int k = 0; k < 2 * C; ++k) A[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(own[k]), nl - 1));
-        }
-        if (nl >= 2) {
-            const float M[4] = {readfirstlane_f(pwv[0]), readfirstlane_f(pwv[1]), readfirstlane_f(pwv[2]), readfirstlane_f(pwv[3])};  // B^v
-            float xp[2 * C];
-#pragma unroll
-            for (int k = 0; k < 2 * C; ++k) xp[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Pq[k]), nl - 2));
-#pragma unroll
-            for (int ch = 0; ch < C; ++ch) mat_acc(M, xp[2 * ch], xp[2 * ch + 1], A[2 * ch], A[2 * ch + 1]);
-        }
+        tile_aggregate(own, Pq, pwv, (int)((n_t + R - 1) / R), A);
         if (lane < 2 * C) {
             float ev = A[0];
 #pragma unroll
@@ -433,14 +394,7 @@ __global__ __launch_bounds__(64 * (kSblkWaves + 1), (NS * KV <= 8 ? 5 : 3)) void
 #pragma unroll
             for (int ch = 0; ch < C; ++ch) mat_acc(kM, __uint_as_float((uint32_t)gvw[2 * ch]), __uint_as_float((uint32_t)gvw[2 * ch + 1]), c[2 * ch], c[2 * ch + 1]);
         }
-#pragma unroll
-        for (int k = 0; k < 2 * C; ++k) {  // sum over lanes 0..31 -> uniform
-            c[k] += dpp0<kDppRowShr + 1, 0xf>(c[k]);
-            c[k] += dpp0<kDppRowShr + 2, 0xf>(c[k]);
-            c[k] += dpp0<kDppRowShr + 4, 0xf>(c[k]);
-            c[k] += dpp0<kDppRowShr + 8, 0xf>(c[k]);
-            c[k] = readlane_f(c[k], 15) + readlane_f(c[k], 31);
-        }
+        half_wave_sum(c);  // sum over lanes 0..31 -> uniform
     }
     if (win_on && q.hand_in) {  // the block in front still runs: its last tile leaves the state as tagged words (it holds a slot or is done: see sblk_try)
         unsigned long long hv[2 * C];
@@ -487,34 +441,13 @@ __global__ __launch_bounds__(64 * (kSblkWaves + 1), (NS * KV <= 8 ? 5 : 3)) void
     }
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) mat_acc(lM, c[2 * ch], c[2 * ch + 1], Q[2 * ch], Q[2 * ch + 1]);  // start state of the lane's run = Q + B^(R*lane) * carry
-    {
-        lds_u8 *row = lds + kRing + (uint32_t)lane * kRow;
+    // out[r] + the homogeneous correction, through wave 1's ring (idle by now); n_t by value: captured by reference it lives in memory a pass longer
+    tile_store<R, C>(lds + kRing, lane, [n_t] { return n_t; }, [&] { return (float *)(uintptr_t)a_out; }, [&](int r) {
+        V y;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            V y;
-#pragma unroll
-            for (int ch = 0; ch < C; ++ch) CH::set(y, ch, fma_(readlane_f(U, 25 + 2 * r), Q[2 * ch], fma_(readlane_f(U, 26 + 2 * r), Q[2 * ch + 1], CH::get(out[r], ch))));
-            if (C == 2) *(lds_f2 *)(row + r * FB) = v2f{CH::get(y, 0), CH::get(y, C - 1)};
-            else *(RH_LDS float *)(row + r * FB) = CH::get(y, 0);
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    {
-        float *ot = (float *)(uintptr_t)a_out;  // this lane's frame of every group of 64
-        for (uint32_t f0 = 0; f0 < n_t; f0 += 64) {
-            const uint32_t f = f0 + (uint32_t)lane;
-            if (f < n_t) {
-                const lds_u8 *src2 = lds + kRing + (f / R) * kRow + (f % R) * FB;
-                if (C == 2) {
-                    const v2f a = *(const lds_f2 *)src2;
-                    *reinterpret_cast<float2 *>(ot + (uint64_t)f0 * 2) = make_float2(a.x, a.y);
-                } else {
-                    ot[f0] = *(const RH_LDS float *)src2;
-                }
-            }
-        }
-    }
+        for (int ch = 0; ch < C; ++ch) CH::set(y, ch, fma_(readlane_f(U, 25 + 2 * r), Q[2 * ch], fma_(readlane_f(U, 26 + 2 * r), Q[2 * ch + 1], CH::get(out[r], ch))));
+        return y;
+    });
 }
 
 struct Inst {

@@ -5,33 +5,26 @@
 #include <type_traits>
 
 #include "rh_common.h"
-
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp0(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, true));
-}
-__device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-constexpr int kRowShr = 0x110, kWaveShr1 = 0x138, kBcast15 = 0x142, kBcast31 = 0x143;
+#include "rh_lanes.h"  // fma_, dpp0 and its control words, readlane_f, mat_acc
 
 // plain sums / maxima over the wave (all values >= 0: zero-fill is neutral)
 __device__ __forceinline__ float wave_excl_sum(float v, float &total) {
-    v += dpp0<kRowShr + 1, 0xf>(v);
-    v += dpp0<kRowShr + 2, 0xf>(v);
-    v += dpp0<kRowShr + 4, 0xf>(v);
-    v += dpp0<kRowShr + 8, 0xf>(v);
-    v += dpp0<kBcast15, 0xa>(v);
-    v += dpp0<kBcast31, 0xc>(v);
+    v += dpp0<kDppRowShr + 1, 0xf>(v);
+    v += dpp0<kDppRowShr + 2, 0xf>(v);
+    v += dpp0<kDppRowShr + 4, 0xf>(v);
+    v += dpp0<kDppRowShr + 8, 0xf>(v);
+    v += dpp0<kDppBcast15, 0xa>(v);
+    v += dpp0<kDppBcast31, 0xc>(v);
     total = readlane_f(v, 63);
-    return dpp0<kWaveShr1, 0xf>(v);
+    return dpp0<kDppWaveShr1, 0xf>(v);
 }
 __device__ __forceinline__ float wave_max(float v) {
-    v = fmaxf(v, dpp0<kRowShr + 1, 0xf>(v));
-    v = fmaxf(v, dpp0<kRowShr + 2, 0xf>(v));
-    v = fmaxf(v, dpp0<kRowShr + 4, 0xf>(v));
-    v = fmaxf(v, dpp0<kRowShr + 8, 0xf>(v));
-    v = fmaxf(v, dpp0<kBcast15, 0xa>(v));
-    v = fmaxf(v, dpp0<kBcast31, 0xc>(v));
+    v = fmaxf(v, dpp0<kDppRowShr + 1, 0xf>(v));
+    v = fmaxf(v, dpp0<kDppRowShr + 2, 0xf>(v));
+    v = fmaxf(v, dpp0<kDppRowShr + 4, 0xf>(v));
+    v = fmaxf(v, dpp0<kDppRowShr + 8, 0xf>(v));
+    v = fmaxf(v, dpp0<kDppBcast15, 0xa>(v));
+    v = fmaxf(v, dpp0<kDppBcast31, 0xc>(v));
     return readlane_f(v, 63);
 }
 
