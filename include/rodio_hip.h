@@ -358,6 +358,45 @@ typedef struct rh_wide_src {
 rh_status rh_wide_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
                             const rh_wide_src *srcs_host, uint32_t n_sources, rh_stream stream);
 
+/* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
+ * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays
+ * -0.0 (rh_mix_sum is the MIXER's ((0 + v0) + v1)) -- and where one side has ended the other side's samples follow VERBATIM, bit for bit
+ * (mix.rs:47-52: not s + 0.0).  dst holds max(na, nb) samples.  Rows start at any 4-byte-aligned address; dst == a and dst == b work in
+ * place; na == 0, nb == 0 and both are legal. */
+rh_status rh_mix_pair(float *dst, const float *a, size_t na, const float *b, size_t nb, rh_stream stream);
+/* ---- UniformSourceIterator::new(src, to_ch, to_rate) over a row that is resident as a whole: src/source/uniform.rs:50-97 -- what Mix::new wraps
+ * its second input in (mix.rs:14-21; the first input's wrapper is the identity on samples).  span_len as rh_resample_linear (0 = None):
+ * every min(span_len, 32768) SAMPLES a fresh converter chain whose last frame comes out verbatim, the last chain over what is left.  A
+ * chain that ends inside a frame (spans of 1000 samples of a 6-channel source; a row that ends in mid-frame) is converted as rodio plays
+ * it (the tail segment of rh_uniform_seg) and the next chain starts behind the cut; rh_resample_linear refuses those.  The segments go
+ * through rh_uniform_segments.  dst_capacity below rh_uniform_row_out_samples(): RH_ERR_INVALID, nothing written. */
+rh_status rh_uniform_row_out_samples(uint64_t n_samples, uint32_t from_ch, uint32_t from_rate, uint32_t to_ch, uint32_t to_rate,
+                                     uint64_t span_len, uint64_t *out_samples);
+rh_status rh_uniform_row(float *dst, uint64_t dst_capacity, const float *src, uint64_t n_samples, uint32_t from_ch, uint32_t from_rate,
+                         uint32_t to_ch, uint32_t to_rate, uint64_t span_len, uint64_t *out_samples, rh_stream stream);
+/* ---- Source::take_crossfade_with(other, duration) (src/source/mod.rs:448, src/source/crossfade.rs:10-23), fused and batched:
+ *        Mix(a.take_duration(d) with set_filter_fadeout(), b.take_duration(d).fade_in(d))
+ * for n_pairs pairs in ONE launch.  `a` starts at the sample where the crossfade begins and sets the output's format; its sample o is
+ * multiplied by remaining.as_millis() as f32 and divided by total.as_millis() as f32 (take.rs:33-41: a duration under 1 ms gives
+ * x * 0 / 0).  `b` is in its own format: TakeDuration (take.rs:96-148), the fade-in ramp at b's own rate (linear_ramp.rs:79-110,
+ * fadein.rs:11-13), then UniformSourceIterator (uniform.rs:50-97) in chains of min(span, 32768) samples, span = what the duration admits
+ * unless b_span_len (0 = None) is shorter (take.rs:180-196, linear_ramp.rs:121-123) -- every chain a fresh converter (math.rs:23-26,
+ * sample_rate.rs:131-201) whose last frame is verbatim, then channels.rs:57-85 -- and the four arms of mix.rs:43-53.  A duration that
+ * expires inside a frame of b ends b's chain in front of the silence that completes the frame (take.rs:109-123), so the output may end
+ * inside a frame.  dst receives rh_crossfade_out_samples() samples (written to out_samples_host[pair] unless that is NULL).
+ * The fused kernel takes b of 1 or 2 channels, a of up to 8, any two rates, admitted sample counts that are whole frames on both sides
+ * and chains of whole frames; any other pair (a cut frame, a 6-channel b, a span that cuts frames) runs through rh_take_duration,
+ * rh_linear_gain_ramp, rh_uniform_row and rh_mix_pair on the stream's scratch: never an error, the same bits, slower.  Zero channels or
+ * rate, or a capacity below rh_crossfade_out_samples(): RH_ERR_INVALID, and no pair of the batch is written. */
+/* A pair travels as RH_CROSSFADE_PAIR_WORDS 64-bit words (a host table, read before the call returns), in this order:
+ *   [0] a: device address of the row in the output's format   [1] a_samples   [2] a_channels   [3] a_rate
+ *   [4] b: device address of the row in its own format         [5] b_samples   [6] b_channels   [7] b_rate
+ *   [8] b_span_len: current_span_len() of b, 0 = None          [9] dst: device address         [10] dst_capacity, in samples */
+enum { RH_CROSSFADE_PAIR_WORDS = 11 };
+rh_status rh_crossfade_out_samples(const uint64_t *pair_host, uint64_t duration_ns, uint64_t *out_samples);
+rh_status rh_crossfade(const uint64_t *pairs_host, uint32_t n_pairs, uint64_t duration_ns, uint64_t *out_samples_host,
+                       rh_stream stream);
+
 /* ---- BltFilter (low_pass / high_pass): src/source/blt.rs:502-544,558-560,397-492.
  * kind: 0 = low_pass, 1 = high_pass.  coeffs5 = {b0,b1,b2,a1,a2} (already divided by a0).
  * state (optional device pointer, 4*channels floats {x1,x2,y1,y2} per channel) carries the

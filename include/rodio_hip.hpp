@@ -2887,6 +2887,206 @@ private:
     bool may_cut_ = false;       // an adapter of the chain can make the stream end inside a frame (may_end_inside_a_frame())
 };
 
+// ---------------------------------------------------------------- Mix, Crossfade: the two-input combinators ----
+/// `Source::mix(other)` (source/mod.rs:255, mix.rs:10-22): channels and rate are the first input's, read at construction; both inputs
+/// run through `UniformSourceIterator::new(_, channels, rate)` -- here a `GpuSource(..).uniform(channels, rate)` each, which is the
+/// identity on the first input's samples -- and Mix::next (mix.rs:43-53) adds them while both run and hands on the longer one's rest
+/// verbatim.  The stream ends when BOTH inputs have ended; the second one may be endless.
+/// A head, not a GpuSource stage: a stage cannot emit an unbounded remainder at flush.  As a DeviceGenerator it feeds a GpuSource chain
+/// or a GpuMixer without leaving the device: each input's chain keeps its blocks on the device (keep_blocks_on_device / read_device)
+/// and rh_mix_pair runs over the two blocks; an input that is itself a GpuSource chain or a DeviceGenerator never crosses to the host
+/// (uploaded_samples() stays 0).  Pulled on the host (next() / read() without defer_reads), the two chains are read on the host and the
+/// four arms run there: the same samples.
+/// Deferred reads: the length of the mix is known only once both inputs have been pulled, so read() in deferred mode DOES the block's
+/// work -- it takes the block from both chains device-to-device, mixes it into a queue in device memory on the Mix's own stream and
+/// returns the count -- and fill_device() hands out the queued samples in order (a device copy on the consumer's stream, behind an
+/// event).  read() therefore hands out exactly the counts fill_device() delivers.
+class Mix : public DeviceGenerator {
+public:
+    Mix(BoxSource a, BoxSource b, std::size_t block_frames = 1u << 15) {
+        if (!a || !b) throw std::invalid_argument("source");
+        ch_ = a->channels();
+        rate_ = a->sample_rate();
+        if (!ch_ || !rate_) throw std::invalid_argument("channels and sample_rate are NonZero in rodio");
+        block_ = (block_frames ? block_frames : 1) * ch_;
+        ua_ = uniformed(std::move(a), block_frames);
+        ub_ = uniformed(std::move(b), block_frames);
+        dur_a_ = ua_->total_duration();  // (captured when the UniformSourceIterator is built: uniform.rs:38)
+        dur_b_ = ub_->total_duration();
+        check(rh_stream_create(&st_), "rh_stream_create");
+        check(rh_event_create(&mixed_), "rh_event_create");
+        check(rh_event_create(&taken_), "rh_event_create");
+    }
+    ~Mix() override {
+        if (st_) (void)rh_stream_synchronize(st_);
+        if (taken_pending_) (void)rh_event_synchronize(taken_);
+        ua_.reset();
+        ub_.reset();
+        if (mixed_) (void)rh_event_destroy(mixed_);
+        if (taken_) (void)rh_event_destroy(taken_);
+        if (st_) (void)rh_stream_destroy(st_);
+    }
+    std::optional<float> next() override {
+        float v;
+        return read(&v, 1) ? std::optional<float>(v) : std::nullopt;
+    }
+    std::size_t read(float *dst, std::size_t n) override {
+        begin(defer_);
+        if (device_) {  // deferred: the block is mixed on the device now, fill_device() hands it out
+            if (!defer_) throw std::logic_error("Mix: the stream started on the device: fill_device()");
+            const std::size_t k = produce_device(n);
+            served_ += k;
+            return k;
+        }
+        std::size_t k = 0;
+        while (k < n) {
+            if (hpos_ == host_.size() && !produce_host()) break;
+            const std::size_t take = std::min(n - k, host_.size() - hpos_);
+            std::memcpy(dst + k, host_.data() + hpos_, take * sizeof(float));
+            hpos_ += take;
+            k += take;
+        }
+        served_ += k;
+        return k;
+    }
+    std::size_t fill_device(float *ddst, std::size_t n, rh_stream stream) override {
+        begin(true);
+        if (!device_) throw std::logic_error("Mix: the stream started on the host: next() / read()");
+        if (!defer_) {  // (nothing was counted ahead: the block is made here)
+            while (queued_ < n && !ended_) (void)produce_device(n - queued_);
+        }
+        const std::size_t k = std::min(n, queued_);
+        if (!k) return 0;
+        check(rh_stream_wait_event(stream, mixed_), "rh_stream_wait_event");
+        check(rh_memcpy_d2d(ddst, queue_.get() + head_, k * sizeof(float), stream), "rh_memcpy_d2d");
+        check(rh_event_record(taken_, stream), "rh_event_record");  // the queue's samples are rewritten only behind this copy
+        taken_pending_ = true;
+        head_ += k;
+        queued_ -= k;
+        if (!defer_) served_ += k;
+        return k;
+    }
+    std::uint16_t channels() const override { return ch_; }
+    std::uint32_t sample_rate() const override { return rate_; }
+    std::optional<std::size_t> current_span_len() const override { return std::nullopt; }  // mix.rs:83-91: both sides are UniformSourceIterators
+    std::optional<Nanos> total_duration() const override {                                  // mix.rs:104-112
+        if (dur_a_ && dur_b_) return std::max(*dur_a_, *dur_b_);
+        return std::nullopt;
+    }
+    bool try_seek(Nanos) override { return false; }  // mix.rs:116-120: NotSupported
+    /// mix.rs:56-67: (max(lower1, lower2), None), the lower bounds the two UniformSourceIterators give where the consumer stands
+    SizeHint size_hint() const override {
+        const std::size_t la = ua_->size_hint_at(served_).lower, lb = ub_->size_hint_at(served_).lower;
+        return SizeHint{std::max(la, lb), std::nullopt};
+    }
+    /// Samples of the two inputs that crossed from the host into device memory (0 for chains that start on the device).
+    std::uint64_t uploaded_samples() const { return ua_->timing().uploaded_samples + ub_->timing().uploaded_samples; }
+    /// ... and the samples their generators made on the device.
+    std::uint64_t generated_samples() const { return ua_->timing().generated_samples + ub_->timing().generated_samples; }
+
+private:
+    std::unique_ptr<GpuSource> uniformed(BoxSource src, std::size_t block_frames) const {
+        std::unique_ptr<GpuSource> chain;
+        if (GpuSource *gs = dynamic_cast<GpuSource *>(src.get()); gs && !gs->started()) {  // a chain goes on as it is: it stays on the device end to end
+            src.release();
+            chain.reset(gs);
+        } else {
+            chain = std::make_unique<GpuSource>(std::move(src), block_frames);
+        }
+        chain->uniform(ch_, rate_);
+        return chain;
+    }
+    void begin(bool on_device) {
+        if (begun_) return;
+        begun_ = true;
+        device_ = on_device;
+        if (device_) {
+            ua_->keep_blocks_on_device();
+            ub_->keep_blocks_on_device();
+        }
+    }
+    bool produce_host() {  // the four arms of mix.rs:43-53 over a block of each input
+        if (ended_) return false;
+        ha_.resize(block_);
+        hb_.resize(block_);
+        const std::size_t na = ua_->read(ha_.data(), block_), nb = ub_->read(hb_.data(), block_), k = std::max(na, nb);
+        host_.resize(k);
+        for (std::size_t i = 0; i < k; ++i) host_[i] = i < na ? (i < nb ? ha_[i] + hb_[i] : ha_[i]) : hb_[i];
+        hpos_ = 0;
+        if (k < block_) ended_ = true;  // (both inputs have ended)
+        return k != 0;
+    }
+    std::size_t produce_device(std::size_t n) {
+        if (ended_ || !n) return 0;
+        if (!queued_) head_ = 0;
+        if (head_ + queued_ + n > queue_.size()) {  // room behind what is queued; what is queued moves along (rare: a consumer that counts far ahead)
+            check(rh_stream_synchronize(st_), "rh_stream_synchronize");
+            if (taken_pending_) check(rh_event_synchronize(taken_), "rh_event_synchronize");
+            detail::DeviceBuf bigger(2 * (queued_ + n) + 64);
+            if (queued_) {
+                check(rh_memcpy_d2d(bigger.get(), queue_.get() + head_, queued_ * sizeof(float), st_), "rh_memcpy_d2d");
+                check(rh_stream_synchronize(st_), "rh_stream_synchronize");
+            }
+            queue_.swap(bigger);
+            head_ = 0;
+        }
+        ta_.reset(n + 64);
+        tb_.reset(n + 64);
+        if (taken_pending_) check(rh_stream_wait_event(st_, taken_), "rh_stream_wait_event");
+        const std::size_t na = ua_->read_device(ta_.get(), n, st_), nb = ub_->read_device(tb_.get(), n, st_), k = std::max(na, nb);
+        if (k) {
+            check(rh_mix_pair(queue_.get() + head_ + queued_, ta_.get(), na, tb_.get(), nb, st_), "rh_mix_pair");
+            check(rh_event_record(mixed_, st_), "rh_event_record");
+        }
+        queued_ += k;
+        if (k < n) ended_ = true;
+        return k;
+    }
+    std::uint16_t ch_ = 0;
+    std::uint32_t rate_ = 0;
+    std::size_t block_ = 0;
+    std::unique_ptr<GpuSource> ua_, ub_;
+    std::optional<Nanos> dur_a_, dur_b_;
+    bool begun_ = false, device_ = false, ended_ = false;
+    std::uint64_t served_ = 0;
+    std::vector<float> ha_, hb_, host_;
+    std::size_t hpos_ = 0;
+    rh_stream st_ = nullptr;
+    void *mixed_ = nullptr, *taken_ = nullptr;
+    bool taken_pending_ = false;
+    detail::DeviceBuf queue_, ta_, tb_;
+    std::size_t head_ = 0, queued_ = 0;
+};
+
+/// `Source::take_crossfade_with(other, duration)` (source/mod.rs:448, crossfade.rs:10-23):
+/// Mix(a.take_duration(d) with set_filter_fadeout(), b.take_duration(d).fade_in(d)), streamed through the stand-alone calls -- a
+/// crossfade is seconds long and comes in a handful of blocks; rh_crossfade is the fused form for batches that are resident.
+/// (A zero duration admits nothing: the fade-in, which LinearGainRamp::new refuses at zero, is left out.)
+class Crossfade : public Mix {
+public:
+    Crossfade(BoxSource a, BoxSource b, Nanos duration, std::size_t block_frames = 1u << 15)
+        : Mix(fading_out(std::move(a), duration, block_frames), fading_in(std::move(b), duration, block_frames), block_frames) {}
+
+private:
+    static BoxSource fading_out(BoxSource a, Nanos d, std::size_t block_frames) {
+        if (!a) throw std::invalid_argument("source");
+        auto chain = std::make_unique<GpuSource>(std::move(a), block_frames);
+        chain->take_duration(d, true);
+        return chain;
+    }
+    static BoxSource fading_in(BoxSource b, Nanos d, std::size_t block_frames) {
+        if (!b) throw std::invalid_argument("source");
+        auto chain = std::make_unique<GpuSource>(std::move(b), block_frames);
+        chain->take_duration(d);
+        if (d.count() > 0) chain->fade_in(d);
+        return chain;
+    }
+};
+inline std::unique_ptr<Mix> mix(BoxSource a, BoxSource b, std::size_t block_frames = 1u << 15) { return std::make_unique<Mix>(std::move(a), std::move(b), block_frames); }
+inline std::unique_ptr<Crossfade> take_crossfade_with(BoxSource a, BoxSource b, Nanos duration, std::size_t block_frames = 1u << 15) {
+    return std::make_unique<Crossfade>(std::move(a), std::move(b), duration, block_frames);
+}
+
 // ---------------------------------------------------------------- GpuMixer: the fused mixer path ----
 /// What rodio spells
 ///     let (mixer, mixed) = mixer::mixer(nz!(2), rate);

@@ -55,6 +55,7 @@ from .source import (  # noqa: F401
     async_status,
     agc_state,
     biquad_batch,
+    crossfade_batch,
     limit_batch,
     biquad_coeffs,
     delay_samples,

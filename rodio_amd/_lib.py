@@ -48,6 +48,9 @@ class WideSrc(C.Structure):
     _fields_ = [("data", C.c_void_p), ("channels", C.c_uint32), ("from_rate", C.c_uint32), ("phase", C.c_uint32), ("frames", C.c_uint64), ("last", C.c_uint32), ("gain", C.c_float)]
 
 
+CROSSFADE_PAIR_WORDS = 11  # RH_CROSSFADE_PAIR_WORDS: a, a_samples, a_channels, a_rate, b, b_samples, b_channels, b_rate, b_span_len, dst, dst_capacity
+
+
 class RlmConfig(C.Structure):
     _fields_ = [("from_rate", C.c_uint32), ("to_rate", C.c_uint32), ("channels", C.c_uint32),
                 ("span_len", C.c_uint64), ("filter_kind", C.c_int32), ("filter_freq", C.c_uint32),
@@ -133,6 +136,11 @@ SIGNATURES = {
     "rh_uniform_segments_dev": (i32, [vp, u32, u64, vp]),
     "rh_mix_sum": (i32, [vp, sz, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), u32, vp]),
     "rh_wide_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, vp]),
+    "rh_mix_pair": (i32, [vp, vp, sz, vp, sz, vp]),
+    "rh_uniform_row_out_samples": (i32, [u64, u32, u32, u32, u32, u64, C.POINTER(u64)]),
+    "rh_uniform_row": (i32, [vp, u64, vp, u64, u32, u32, u32, u32, u64, C.POINTER(u64), vp]),
+    "rh_crossfade_out_samples": (i32, [C.POINTER(u64), u64, C.POINTER(u64)]),
+    "rh_crossfade": (i32, [C.POINTER(u64), u32, u64, C.POINTER(u64), vp]),
     "rh_biquad_coeffs": (i32, [i32, u32, f32, u32, f32p]),
     "rh_biquad": (i32, [vp, vp, u64, u32, u32, f32p, vp, i32, vp]),
     "rh_limit": (i32, [vp, vp, u64, u32, u32, u32, C.POINTER(LimitParams), vp, vp]),

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "librodio_hip.so")
-SOURCES = ["rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_limit.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip", "rh_generators.hip", "rh_noise.hip"]
+SOURCES = ["rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_limit.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip", "rh_generators.hip", "rh_noise.hip", "rh_mix2.hip"]
 # -ffp-contract=off: the reference's f32 expressions (lerp, biquad, mixer sum) must not be
 # fused; kernels that want an FMA spell it __builtin_fmaf.
 # -fno-slp-vectorize: hipcc's SLP pass pairs the two stereo channels into v_pk_*_f32; on gfx950
@@ -42,7 +42,7 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "rh_common.h"), os.path.join(CSRC, "rh_lanes.h"), os.path.join(CSRC, "rh_scan_common.h"), os.path.join(CSRC, "rh_pipeline_internal.h"), os.path.join(CSRC, "rh_pipeline_dev.h"), os.path.join(CSRC, "rh_generators.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(HERE, "..", "include", "rodio_hip.h")]
+    headers = [os.path.join(CSRC, "rh_common.h"), os.path.join(CSRC, "rh_lanes.h"), os.path.join(CSRC, "rh_scan_common.h"), os.path.join(CSRC, "rh_pipeline_internal.h"), os.path.join(CSRC, "rh_pipeline_dev.h"), os.path.join(CSRC, "rh_generators.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(CSRC, "rh_rows_dev.h"), os.path.join(HERE, "..", "include", "rodio_hip.h")]
     cc = hipcc()
     jobs = []
     objs = []
@@ -66,6 +66,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     build_live_test(force, run)
     build_generators_test(force, run)
     build_noise_test(force, run)
+    build_mix_test(force, run)
     return LIB
 
 
@@ -146,6 +147,26 @@ def build_noise_test(force: bool, run) -> str:
              "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
     fakes = [os.path.join(root, "tests", "cpp", "fake_device.cpp"), os.path.join(root, "tests", "cpp", "fake_noise.cpp")]
     fexe = os.path.join(root, "tests", "cpp", "noise_mirror_test_fake")
+    if force or _stale(fexe, [msrc] + fakes + hdrs):
+        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
+    return mexe
+
+
+def build_mix_test(force: bool, run) -> str:
+    """tests/cpp/mix_mirror_test.cpp: the C++ mirror's Mix and Crossfade (include/rodio_hip.hpp) against the library (mix_mirror_test), and
+    against the CPU stand-ins (fake_device.cpp + fake_generators.cpp + fake_noise.cpp + fake_mix.cpp: mix_mirror_test_fake).  TEST
+    INFRASTRUCTURE: plain g++."""
+    root = os.path.join(HERE, "..")
+    inc = os.path.join(root, "include")
+    msrc = os.path.join(root, "tests", "cpp", "mix_mirror_test.cpp")
+    mexe = os.path.join(root, "tests", "cpp", "mix_mirror_test")
+    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(CSRC, "rh_generators.h")]
+    gxx = shutil.which("g++") or "g++"
+    if force or _stale(mexe, [msrc, LIB] + hdrs):
+        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
+             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
+    fakes = [os.path.join(root, "tests", "cpp", f) for f in ("fake_device.cpp", "fake_generators.cpp", "fake_noise.cpp", "fake_mix.cpp")]
+    fexe = os.path.join(root, "tests", "cpp", "mix_mirror_test_fake")
     if force or _stale(fexe, [msrc] + fakes + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
     return mexe

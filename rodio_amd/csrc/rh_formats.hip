@@ -10,6 +10,7 @@
 // 512 B per wave-instruction).
 #include "rh_common.h"
 #include "rh_noise.h"
+#include "rh_rows_dev.h"
 
 namespace {
 
@@ -89,21 +90,15 @@ __global__ __launch_bounds__(kBlock) void k_dither(float *__restrict__ dst, cons
 // LinearGainRamp (fade_in / fade_out): src/source/linear_ramp.rs:79-110.  The iterator's `elapsed` is a
 // pure function of the frame index while the ramp runs (f * (1e9 / rate) ns), so the op is stateless:
 // sample k0+i of the stream is in frame (k0+i)/channels.
-__device__ __forceinline__ float secs_f32(uint64_t ns) { return (float)(ns / 1000000000ull) + (float)(uint32_t)(ns % 1000000000ull) / 1000000000.0f; }
+// (the factor of a frame: rhrows::ramp_factor, shared with the fused crossfade)
 // (a lane's four samples: ONE 64-bit division finds the first one's frame, the others follow by counting channels)
-__global__ __launch_bounds__(kBlock) void k_linear_gain_ramp(float *__restrict__ dst, const float *__restrict__ src, size_t n, uint64_t k0, uint32_t channels, uint64_t step_ns,
-                                                             uint64_t done_frame, float total_s, float start_gain, float end_gain, float after, int vec_ok) {
+__global__ __launch_bounds__(kBlock) void k_linear_gain_ramp(float *__restrict__ dst, const float *__restrict__ src, size_t n, uint64_t k0, uint32_t channels, const rhrows::Ramp ramp, int vec_ok) {
     const size_t nvec = (n + 3) / 4, stride = (size_t)gridDim.x * kBlock;
     for (size_t v = (size_t)blockIdx.x * kBlock + threadIdx.x; v < nvec; v += stride) {
         const size_t i = 4 * v;
         uint64_t frame = (k0 + i) / channels;
         uint32_t c = (uint32_t)((k0 + i) - frame * channels);
-        auto factor_of = [&](uint64_t fr) {
-            // elapsed >= total  <=>  frame >= ceil(total / step) (done_frame; never when the step is 0)
-            if (step_ns != 0 && fr >= done_frame) return after;
-            const float p = secs_f32(fr * step_ns) / total_s;
-            return start_gain * (1.0f - p) + end_gain * p;
-        };
+        auto factor_of = [&](uint64_t fr) { return rhrows::ramp_factor(ramp, fr); };
         float factor = factor_of(frame);
         float x[4], y[4];
         const bool whole = i + 4 <= n, vec = (vec_ok & 2) && whole;  // (vec_ok: rh::rows_vec_bits)
@@ -150,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void k_take_duration(float *__restrict__ ds
     const float total = (float)(requested_ns / 1000000ull);
     auto one = [=](size_t i, float x) {
         float v = x;
-        if (fade) v = v * (float)((rem0_ns - i * dps_ns) / 1000000ull) / total;
+        if (fade) v = rhrows::take_fade(v, rem0_ns - i * dps_ns, total);
         return v;
     };
     rh::map4<kBlock>(dst, src, (size_t)take, vec_ok, one);
@@ -226,11 +221,8 @@ rh_status rh_linear_gain_ramp(float *dst, const float *src, size_t n, uint64_t s
     if (channels == 0 || sample_rate == 0 || duration_ns == 0) return RH_ERR_INVALID;  // linear_ramp.rs:34 asserts a non-zero duration
     if (n == 0) return RH_OK;
     if (!dst || !src) return RH_ERR_INVALID;
-    const uint64_t step_ns = 1000000000ull / sample_rate;  // linear_ramp.rs:98-100 (0 above 1 GHz: the ramp never advances)
-    const float total_s = (float)(duration_ns / 1000000000ull) + (float)(uint32_t)(duration_ns % 1000000000ull) / 1000000000.0f;
-    const uint64_t done_frame = step_ns ? (duration_ns + step_ns - 1) / step_ns : 0;  // elapsed >= total from this frame on
-    hipLaunchKernelGGL(k_linear_gain_ramp, dim3(rh::grid_tiles((n + 3) / 4)), dim3(kBlock), 0, rh::as_stream(stream), dst, src, n, sample_offset, channels, step_ns, done_frame, total_s, start_gain,
-                       end_gain, clamp_end ? end_gain : 1.0f, rh::rows_vec_bits(dst, src));
+    hipLaunchKernelGGL(k_linear_gain_ramp, dim3(rh::grid_tiles((n + 3) / 4)), dim3(kBlock), 0, rh::as_stream(stream), dst, src, n, sample_offset, channels,
+                       rhrows::make_ramp(sample_rate, duration_ns, start_gain, end_gain, clamp_end != 0), rh::rows_vec_bits(dst, src));
     RH_CHECK_LAUNCH();
     return RH_OK;
 }

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "rh_common.h"
+#include "rh_rows_dev.h"
 
 namespace {
 
@@ -34,11 +35,7 @@ struct SegTable {
     rh_uniform_seg s[kSegsPerLaunch];
 };
 
-// #m with floor(m*F/T) <= n-2 (both taps of the lerp exist)
-__host__ __device__ inline uint64_t lerp_ready(uint64_t n, uint64_t F, uint64_t T) {
-    if (n == 0) return 0;
-    return (uint64_t)((((unsigned __int128)(n - 1) * T) + F - 1) / F);
-}
+using rhrows::lerp_ready;  // #m with floor(m*F/T) <= n-2 (both taps of the lerp exist)
 // The tail of a span of q whole frames that ends inside a frame (rodio_hip.h): the output frames m_first .. m_first + k - 1 have their
 // first tap on the last whole frame and lerp towards the cut frame (k may be 0: downsampling can skip that frame, and a span without
 // a whole frame has none); e = 1 when an output lands on the cut frame itself, which then comes out verbatim.
@@ -88,7 +85,7 @@ __device__ __forceinline__ void convert_cut_tail(const rh_uniform_seg &g, uint32
                 const unsigned __int128 pp = (unsigned __int128)(mf + r) * F;
                 const uint32_t num = (uint32_t)(pp % T);
                 const float av = last[c] * g.gain;
-                v = av + (pv - av) * (float)num / Tf;  // math.rs:25
+                v = rhrows::lerp(av, pv, (float)num, Tf);  // math.rs:25
             }
         }
         g.dst[j - g.m0] = v;
@@ -130,7 +127,7 @@ __device__ __forceinline__ void convert_frames(const rh_uniform_seg &g, uint32_t
             float v = av;
             if (!verbatim) {
                 const float bv = a[fc + k] * g.gain;
-                v = av + (bv - av) * numf / Tf;
+                v = rhrows::lerp(av, bv, numf, Tf);
             }
             o[k] = v;
         }

@@ -219,6 +219,35 @@ class GpuSource:
                          _stream()), "rh_agc")
         return GpuSource(out, self._channels, self._sample_rate, self.span_len)
 
+    def mix(self, other: "GpuSource") -> "GpuSource":
+        """Source::mix (src/source/mod.rs:255, mix.rs:10-22,43-53): both inputs as UniformSourceIterators in THIS source's format --
+        the identity on this one's samples, the span-by-span conversion of uniform.rs:50-97 on `other` -- then s1 + s2 while both run
+        and the longer one's rest verbatim (rh_mix_pair).  current_span_len() behind it is None (mix.rs:83-91)."""
+        if not isinstance(other, GpuSource):
+            raise TypeError("mix() takes a GpuSource")
+        _ensure()
+        b = _uniform_row(other, self._channels, self._sample_rate)
+        admits = getattr(self, "_admits", None)  # (the identity wrapper never asks a TakeDuration for the silence that completes a cut frame)
+        na, nb = len(self) if admits is None else min(admits, len(self)), int(b.numel())
+        out = _dev_empty(max(na, nb))
+        check(lib.rh_mix_pair(_ptr(out), _ptr(self.samples), na, _ptr(b), nb, _stream()), "rh_mix_pair")
+        return GpuSource(out, self._channels, self._sample_rate, None)
+
+    def take_crossfade_with(self, other: "GpuSource", duration_ns: int) -> "GpuSource":
+        """Source::take_crossfade_with (src/source/mod.rs:448, crossfade.rs:10-23): mix(self.take_duration(d) with the fade-out
+        filter, other.take_duration(d).fade_in(d)), through the stand-alone calls (crossfade_batch is the fused form)."""
+        if not isinstance(other, GpuSource):
+            raise TypeError("take_crossfade_with() takes a GpuSource")
+        if duration_ns < 0:
+            raise ValueError("a Duration is not negative")
+        a = self.take_duration(duration_ns, True)
+        b = other.take_duration(duration_ns)
+        if b._admits:  # (LinearGainRamp::new refuses a zero duration, which admits nothing)
+            admits, b = b._admits, b.fade_in(duration_ns)
+            b._admits = admits
+        return a.mix(b)
+
+
 
 def _upload(samples):
     torch = _t()
@@ -303,6 +332,46 @@ def UniformSourceIterator(inp: GpuSource, channels: int, sample_rate: int) -> Gp
         span = 0
     r = SampleRateConverter(inp, inp.sample_rate(), sample_rate, inp.channels(), span)
     return ChannelCountConverter(r, inp.channels(), channels)
+
+
+def _uniform_row(inp: GpuSource, channels: int, sample_rate: int):
+    """UniformSourceIterator over the whole row as rh_uniform_row runs it: chains that cut a frame included."""
+    admits = getattr(inp, "_admits", None)
+    n = len(inp) if admits is None else min(admits, len(inp))  # (a TakeDuration answers Some(0) behind what it admits)
+    span = inp.current_span_len() or 0
+    m = C.c_uint64(0)
+    check(lib.rh_uniform_row_out_samples(n, inp.channels(), inp.sample_rate(), channels, sample_rate, span, C.byref(m)), "rh_uniform_row_out_samples")
+    out = _dev_empty(m.value)
+    check(lib.rh_uniform_row(_ptr(out), m.value, _ptr(inp.samples), n, inp.channels(), inp.sample_rate(), channels, sample_rate, span, C.byref(m),
+                             _stream()), "rh_uniform_row")
+    return out
+
+
+def crossfade_batch(a, b, duration_ns: int):
+    """rh_crossfade: a[k].take_crossfade_with(b[k], duration) for every pair of the two lists in one call (one launch for the pairs
+    the fused kernel takes).  Returns the crossfades as GpuSources in a[k]'s format."""
+    a, b = list(a), list(b)
+    if len(a) != len(b):
+        raise ValueError("crossfade_batch takes as many second inputs as first ones")
+    if any(not isinstance(x, GpuSource) for x in a + b):
+        raise TypeError("crossfade_batch takes GpuSources")
+    if duration_ns < 0:
+        raise ValueError("a Duration is not negative")
+    if not a:
+        return []
+    _ensure()
+    W = _lib.CROSSFADE_PAIR_WORDS
+    pairs = (C.c_uint64 * (W * len(a)))()
+    outs = []
+    for k, (x, y) in enumerate(zip(a, b)):
+        pairs[W * k: W * k + 9] = [x.samples.data_ptr(), len(x), x.channels(), x.sample_rate(), y.samples.data_ptr(), len(y), y.channels(), y.sample_rate(), y.current_span_len() or 0]
+        m = C.c_uint64(0)
+        check(lib.rh_crossfade_out_samples(C.cast(C.byref(pairs, 8 * W * k), C.POINTER(C.c_uint64)), duration_ns, C.byref(m)), "rh_crossfade_out_samples")
+        outs.append(_dev_empty(m.value))
+        pairs[W * k + 9], pairs[W * k + 10] = outs[-1].data_ptr(), m.value
+    got = (C.c_uint64 * len(a))()
+    check(lib.rh_crossfade(pairs, len(a), duration_ns, got, _stream()), "rh_crossfade")
+    return [GpuSource(o[: got[k]], x.channels(), x.sample_rate(), None) for k, (o, x) in enumerate(zip(outs, a))]
 
 
 _CONV = {

@@ -25,7 +25,9 @@
 //!
 //! This is the Rust twin of `include/rodio_hip.hpp` (C++17, compiled and tested in the repository: `tests/test_host_mirror.py`),
 //! method for method (`tests/test_rust_decls.py` compares the two); the image the library was developed in has no Rust toolchain,
-//! so this crate has been checked against the header and against its twin but not against `rustc`.
+//! so this crate has been checked against the header and against its twin but not against `rustc`.  That holds for [`GpuMix`],
+//! [`mix`] and [`take_crossfade_with`] as for everything else here.  The generator of [`ffi`] gives every constant of the header's
+//! enums the type `RhStatus` (`i32`), counts such as `RH_CROSSFADE_PAIR_WORDS` included: cast them (`as usize`) where they size a table.
 
 pub mod ffi;
 
@@ -2498,4 +2500,101 @@ impl GpuVelvet {
     pub fn new_with_density(sample_rate: SampleRate, density: std::num::NonZeroU32, seed: u64) -> Self {
         GpuVelvet(GpuNoise::with_seed(NoiseKind::Velvet, sample_rate, seed, density.get()))
     }
+}
+
+// ------------------------------------------------------------------------------------------------ Mix, Crossfade ----
+/// `Source::mix(other)` (`source/mod.rs:255`, `mix.rs:10-22,43-53`) on the device: the twin of `rodio_hip::Mix`.  Channels and rate are the
+/// first input's, read at construction; both inputs run as `GpuSource::new(_, block).uniform(channels, rate)` -- the identity on the
+/// first one's samples -- whose blocks stay in device memory (`keep_blocks_on_device` / `read_device`), and `rh_mix_pair` runs the four
+/// arms of `Mix::next` over the two blocks: `s1 + s2` while both run, the longer one's rest verbatim; the stream ends when BOTH have
+/// ended.  A head, not a stage (the second input may be endless): as a `DeviceGenerator` it feeds a chain without leaving the device;
+/// `next()` serves blocks from page-locked memory.
+pub struct GpuMix<A: Source, B: Source> {
+    a: GpuSource<A>, b: GpuSource<B>, ch: u16, rate: u32, dur_a: Option<Duration>, dur_b: Option<Duration>, ended: bool, served: u64,
+    stream: RhStream, ta: DeviceBuf, tb: DeviceBuf, dblock: DeviceBuf, block: PinnedBuf, pos: usize, len: usize, block_samples: usize,
+}
+unsafe impl<A: Source + Send, B: Source + Send> Send for GpuMix<A, B> {}
+impl<A: Source, B: Source> GpuMix<A, B> {
+    pub fn new(a: A, b: B, block_frames: usize) -> Self {
+        let (channels, sample_rate) = (a.channels(), a.sample_rate());   // mix.rs:14-15
+        Self::of_chains(GpuSource::new(a, block_frames), GpuSource::new(b, block_frames), channels, sample_rate, block_frames)
+    }
+    /// Over two chains that have not started (`src.take_duration(..)`, a chain over a generator): they go on as they are.
+    pub fn of_chains(a: GpuSource<A>, b: GpuSource<B>, channels: ChannelCount, sample_rate: SampleRate, block_frames: usize) -> Self {
+        let (mut a, mut b) = (a.uniform(channels, sample_rate), b.uniform(channels, sample_rate));
+        let (dur_a, dur_b) = (a.total_duration(), b.total_duration());   // captured when the UniformSourceIterator is built (uniform.rs:38)
+        a.keep_blocks_on_device(true);
+        b.keep_blocks_on_device(true);
+        let mut stream: RhStream = ptr::null_mut();
+        ck(unsafe { rh_stream_create(&mut stream) }, "rh_stream_create");
+        GpuMix { a, b, ch: channels.get(), rate: sample_rate.get(), dur_a, dur_b, ended: false, served: 0, stream, ta: DeviceBuf::new(), tb: DeviceBuf::new(),
+                 dblock: DeviceBuf::new(), block: PinnedBuf::new(), pos: 0, len: 0, block_samples: block_frames.max(1) * channels.get() as usize }
+    }
+    /// Samples of the two inputs that crossed from the host into device memory (0 for chains that start on the device).
+    pub fn uploaded_samples(&self) -> u64 { self.a.timing().uploaded_samples + self.b.timing().uploaded_samples }
+}
+impl<A: Source, B: Source> DeviceGenerator for GpuMix<A, B> {
+    fn fill_device(&mut self, ddst: *mut f32, n: usize, stream: RhStream) -> usize {
+        if n == 0 || self.ended { return 0; }
+        self.ta.reserve(n + 64);
+        self.tb.reserve(n + 64);
+        let na = self.a.read_device(self.ta.p, n, stream);
+        let nb = self.b.read_device(self.tb.p, n, stream);
+        let k = na.max(nb);
+        if k > 0 { ck(unsafe { rh_mix_pair(ddst, self.ta.p, na, self.tb.p, nb, stream) }, "rh_mix_pair"); }
+        if k < n { self.ended = true; }   // both inputs have ended
+        k
+    }
+}
+impl<A: Source, B: Source> Iterator for GpuMix<A, B> {
+    type Item = f32;
+    fn next(&mut self) -> Option<f32> {
+        if self.pos == self.len {
+            let n = self.block_samples;
+            self.block.reserve(n);
+            self.dblock.reserve(n);
+            let (d, s) = (self.dblock.p, self.stream);
+            let k = self.fill_device(d, n, s);
+            if k == 0 { return None; }
+            unsafe {
+                ck(rh_memcpy_d2h(self.block.p.cast(), d.cast(), k * 4, s), "rh_memcpy_d2h");
+                ck(rh_stream_synchronize(s), "rh_stream_synchronize");
+            }
+            self.pos = 0;
+            self.len = k;
+        }
+        let v = unsafe { *self.block.p.add(self.pos) };
+        self.pos += 1;
+        self.served += 1;
+        Some(v)
+    }
+    /// mix.rs:56-67: (max(lower1, lower2), None), the lower bounds the two `uniform` chains give where the consumer stands
+    fn size_hint(&self) -> (usize, Option<usize>) { (self.a.size_hint_at(self.served).0.max(self.b.size_hint_at(self.served).0), None) }
+}
+impl<A: Source, B: Source> Source for GpuMix<A, B> {
+    fn current_span_len(&self) -> Option<usize> { None }   // mix.rs:83-91
+    fn channels(&self) -> ChannelCount { ChannelCount::new(self.ch).unwrap() }
+    fn sample_rate(&self) -> SampleRate { SampleRate::new(self.rate).unwrap() }
+    fn total_duration(&self) -> Option<Duration> {   // mix.rs:104-112
+        match (self.dur_a, self.dur_b) { (Some(x), Some(y)) => Some(x.max(y)), _ => None }
+    }
+    fn try_seek(&mut self, _pos: Duration) -> Result<(), SeekError> {   // mix.rs:116-120
+        Err(SeekError::NotSupported { underlying_source: "rodio_hip::GpuMix" })
+    }
+}
+impl<A: Source, B: Source> Drop for GpuMix<A, B> { fn drop(&mut self) { unsafe { rh_stream_synchronize(self.stream); rh_stream_destroy(self.stream); } } }
+
+/// `Source::mix(other)`: `mix(a, b)` is `a.mix(b)`.
+pub fn mix<A: Source, B: Source>(a: A, b: B) -> GpuMix<A, B> { GpuMix::new(a, b, 1 << 15) }
+/// `Source::take_crossfade_with(other, duration)` (`source/mod.rs:448`, `crossfade.rs:10-23`):
+/// `Mix(a.take_duration(d)` with the fade-out filter`, b.take_duration(d).fade_in(d))`, streamed through the stand-alone calls
+/// (`rh_crossfade` is the fused form for resident batches).  A zero duration admits nothing: the fade-in, which
+/// `LinearGainRamp::new` refuses at zero, is left out.
+pub fn take_crossfade_with<A: Source, B: Source>(a: A, b: B, duration: Duration) -> GpuMix<A, B> {
+    let block_frames = 1 << 15;
+    let (channels, sample_rate) = (a.channels(), a.sample_rate());
+    let fading_out = GpuSource::new(a, block_frames).take_duration(duration, true);
+    let mut fading_in = GpuSource::new(b, block_frames).take_duration(duration, false);
+    if !duration.is_zero() { fading_in = fading_in.fade_in(duration); }
+    GpuMix::of_chains(fading_out, fading_in, channels, sample_rate, block_frames)
 }
