@@ -42,7 +42,8 @@ def _stale(target: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "rh_common.h"), os.path.join(CSRC, "rh_lanes.h"), os.path.join(CSRC, "rh_scan_common.h"), os.path.join(CSRC, "rh_pipeline_internal.h"), os.path.join(CSRC, "rh_pipeline_dev.h"), os.path.join(CSRC, "rh_generators.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(CSRC, "rh_rows_dev.h"), os.path.join(HERE, "..", "include", "rodio_hip.h")]
+    # every header: one that is left out here means a stale .so wherever the tree is built next
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", "rodio_hip.h")]
     cc = hipcc()
     jobs = []
     objs = []
@@ -67,6 +68,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     build_generators_test(force, run)
     build_noise_test(force, run)
     build_mix_test(force, run)
+    build_scan_launch_test(force, run)
     return LIB
 
 
@@ -170,6 +172,19 @@ def build_mix_test(force: bool, run) -> str:
     if force or _stale(fexe, [msrc] + fakes + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
     return mexe
+
+
+def build_scan_launch_test(force: bool, run) -> str:
+    """tests/cpp/scan_launch_test.cpp: the scan kernels' host protocol (csrc/rh_scan_launch.h: variant pick, scratch layout, the launch that needs no
+    initialisation in front of it, table rotation, ticket base) against a model of the device (TEST INFRASTRUCTURE: plain g++, no library)."""
+    root = os.path.join(HERE, "..")
+    src = os.path.join(root, "tests", "cpp", "scan_launch_test.cpp")
+    exe = os.path.join(root, "tests", "cpp", "scan_launch_test")
+    if not os.path.exists(src):  # the library does not need the driver: a tree whose tests/ lacks it (an older suite run on this library) still builds
+        return exe
+    if force or _stale(exe, [src, os.path.join(CSRC, "rh_scan_launch.h")]):
+        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I", CSRC, src, "-o", exe])
+    return exe
 
 
 if __name__ == "__main__":

@@ -33,7 +33,6 @@ namespace {
 #include "rh_scan_common.h"
 
 constexpr int kMaxR = 16, kMaxNW = 8;
-constexpr uint32_t kSpinLimit = 1u << 22;
 
 struct BqTabs {  // per lane (device memory, cached per filter and geometry): powers of B, row-major 2x2
     float laneM[64][4];  // B^(R*l)
@@ -46,13 +45,13 @@ struct BqArgs {
     const float *src;
     float *gran;            // [S][tiles][2*C] hand-off words: the tiles' zero-state aggregates (scan basis)
     float *gran_other;      // the table of the NEXT launch on this stream (the two alternate): a tile that is done sets its record there back to
-                            // "not yet", so that launch needs no kernel in front of it (nullptr: it initialises its own); rh_limit.hip has the same
+                            // "not yet", so that launch needs no kernel in front of it (nullptr: it initialises its own); the protocol: rh_scan_launch.h
     uint32_t ticket_base;   // value of ctl[0] when this launch starts (the counter is never reset)
     const float *state_in;  // [S][C][4] {x1,x2,y1,y2} snapshot, or nullptr (zero state)
     const BqTabs *tabs;
     uint32_t *ctl;          // [0] ticket
     uint32_t *status;          // the library's sticky failure word (rh_async_status)
-    uint32_t spin;             // polls of one hand-off before the tile gives up (kSpinLimit; RH_SCAN_SPIN_LIMIT overrides)
+    uint32_t spin;             // polls of one hand-off before the tile gives up (rh::kSpinLimit; RH_SCAN_SPIN_LIMIT overrides)
     uint32_t dma_top;          // 1: the next tile's samples are requested at the top of a tile, not right in front of its poll
     uint64_t frames, stride;
     uint32_t n_streams, tiles, J;
@@ -446,10 +445,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 4 ? (C * R <= 16 ? 4 : 2) : 1)) voi
 __global__ void k_bq_pre(uint32_t *ctl, uint32_t *words, uint64_t n_words, float *snap, float *xlast, const float *state, const float *src, uint64_t frames, uint64_t stride,
                          uint32_t C, uint32_t n) {
     const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
-    // the scratch of the launch: control words zeroed, every hand-off word "not yet" -- by a kernel, in the stream's own buffer
-    // (why not hipMemsetAsync on hipMallocAsync memory: rh_limit.hip, k_limit_init)
-    if (i0 < 16) ctl[i0] = 0u;
-    for (uint64_t i = i0; i < n_words; i += step) words[i] = 0xffffffffu;
+    scan_scratch_init(ctl, words, n_words, i0, step);
     if (!state) return;
     for (uint64_t i = i0; i < n; i += step) {  // (stream, channel)
         const uint32_t s = (uint32_t)i / C, c = (uint32_t)i - s * C;
@@ -615,36 +611,16 @@ rh_status biquad_scan_launch(float *dst, const float *src, uint64_t frames, uint
     const uint64_t stride = frames * channels;
     const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0 && (n_streams == 1 || stride % 4 == 0);
     if (!aligned) return RH_ERR_UNSUPPORTED;
-    // Geometry: the longest tile a stream fills at least half of, more frames per lane among equals (rh_limit.hip has the
-    // measurements: 8192-frame tiles from 64 x 1 Mi frames down to 256 x 8192, 0.240 ms with R = 16 against 0.261 ms with R = 8)
-    const BqVariant *v = nullptr;
-    if (rh::knob(rh::K_BIQUAD_R) || rh::knob(rh::K_BIQUAD_NW)) {  // tuning aids: the variant closest to the request
-        const int want_R = rh::knob(rh::K_BIQUAD_R) ? atoi(rh::knob(rh::K_BIQUAD_R)) : 16, want_NW = rh::knob(rh::K_BIQUAD_NW) ? atoi(rh::knob(rh::K_BIQUAD_NW)) : 8;
-        for (const BqVariant &c : kVariants) {
-            if (c.C != (int)channels) continue;
-            auto score = [&](const BqVariant &x) { return 10 * std::abs(x.NW - want_NW) + std::abs(x.R - want_R); };
-            if (!v || score(c) < score(*v)) v = &c;
-        }
-    } else {
-        auto tile_of = [](const BqVariant &x) { return (uint64_t)64 * x.R * x.NW; };
-        for (const BqVariant &c : kVariants) {
-            if (c.C != (int)channels) continue;
-            if (!v) {
-                v = &c;
-                continue;
-            }
-            const bool fits_c = tile_of(c) <= 2 * frames, fits_v = tile_of(*v) <= 2 * frames;
-            const bool better = fits_c != fits_v ? fits_c
-                                : (fits_c ? (tile_of(c) > tile_of(*v) || (tile_of(c) == tile_of(*v) && c.R > v->R)) : tile_of(c) < tile_of(*v));
-            if (better) v = &c;
-        }
-    }
+    // Geometry: rh::scan::pick_variant
+    const rh::scan::Request want{rh::knob(rh::K_BIQUAD_R) ? atoi(rh::knob(rh::K_BIQUAD_R)) : 16, rh::knob(rh::K_BIQUAD_NW) ? atoi(rh::knob(rh::K_BIQUAD_NW)) : 8};
+    const bool by_request = rh::knob(rh::K_BIQUAD_R) || rh::knob(rh::K_BIQUAD_NW);  // tuning aids
+    const BqVariant *v = rh::scan::pick_variant(kVariants, channels, frames, by_request ? &want : nullptr, [](const BqVariant &) { return true; });
     if (!v) return RH_ERR_UNSUPPORTED;
     const std::shared_ptr<const BqPlan> pl = get_plan(co, v->R, v->NW);
     if (!pl) return RH_ERR_UNSUPPORTED;
-    const uint32_t R = (uint32_t)v->R, NW = (uint32_t)v->NW, LW = 64u * R * NW;
+    const uint32_t NW = (uint32_t)v->NW, LW = 64u * (uint32_t)v->R * NW;
     const uint64_t tiles64 = (frames + LW - 1) / LW;
-    if (tiles64 > 0x7fffffffull || tiles64 * n_streams >= 0xfff00000ull) return RH_ERR_UNSUPPORTED;
+    if (!rh::scan::tickets_fit(tiles64, n_streams)) return RH_ERR_UNSUPPORTED;
 
     BqArgs a = pl->proto;
     a.dst = dst;
@@ -655,68 +631,20 @@ rh_status biquad_scan_launch(float *dst, const float *src, uint64_t frames, uint
     a.n_streams = n_streams;
     a.tiles = (uint32_t)tiles64;
     const size_t n_sc = (size_t)n_streams * channels;
-    // two hand-off tables in rotation, as in rh_limit.hip: a launch without a carried state that follows one of its own shape on this
-    // stream finds its table cleared by that launch and needs no k_bq_pre in front of it
-    const size_t gran_bytes = (((size_t)n_streams * tiles64 * 2 * channels * sizeof(float)) + 63) & ~size_t(63);
-    const size_t head = 64 + ((n_sc * 6 * 4 + 63) & ~size_t(63));  // control words, state snapshot [n][4], last inputs [n][2]
-    unsigned char *scratch = nullptr;
+    // the scratch's head: state snapshot [n][4], last inputs [n][2], taken by k_bq_pre (a carried state always has that kernel in front)
+    float *snap = nullptr, *xlast = nullptr;
     std::unique_lock<std::mutex> scratch_hold;
-    rh::ScratchAux *aux = nullptr;
-    RH_HIP_TRY(rh::stream_scratch(s, head + 2 * gran_bytes, reinterpret_cast<void **>(&scratch), scratch_hold, &aux));
-    uint64_t tag = 0x4251554144ull;  // "BQUAD", then the shape (FNV-1a)
-    for (uint64_t v_ : {(uint64_t)n_streams, tiles64, (uint64_t)channels, (uint64_t)head, (uint64_t)gran_bytes, (uint64_t)reinterpret_cast<uintptr_t>(scratch)}) tag = (tag ^ v_) * 0x100000001b3ull;
-    tag |= 1;
-    const char *init_knob = rh::knob(rh::K_LIMIT_INIT);  // RH_LIMIT_INIT=1: both scan kernels initialise their tables in front of every launch
-    const bool clean = !state && aux->tag == tag && !(init_knob && init_knob[0] == '1');
-    a.ctl = reinterpret_cast<uint32_t *>(scratch);
-    a.status = rh::g_async_status;
-    a.dma_top = rh::knob(rh::K_SCAN_DMA_TOP) ? (uint32_t)atoi(rh::knob(rh::K_SCAN_DMA_TOP)) : 1u;  // measured: 0.312 -> 0.286 ms (limiter), 0.234 -> 0.221 ms (biquad), 64 x 1 Mi frames
-    a.spin = rh::knob(rh::K_SCAN_SPIN_LIMIT) ? (uint32_t)strtoul(rh::knob(rh::K_SCAN_SPIN_LIMIT), nullptr, 10) : kSpinLimit;
-    float *snap = reinterpret_cast<float *>(scratch + 64), *xlast = snap + n_sc * 4;
-    hipError_t e = hipSuccess;
-    if (!clean) {
-        const uint64_t n_words = 2 * gran_bytes / 4;
-        const unsigned pre_wgs = (unsigned)std::min<uint64_t>(1024, (std::max<uint64_t>(n_words, n_sc) + 255) / 256);
-        hipLaunchKernelGGL(k_bq_pre, dim3(pre_wgs), dim3(256), 0, s, a.ctl, reinterpret_cast<uint32_t *>(scratch + head), n_words, snap, xlast, state, src, frames, stride, channels, (uint32_t)n_sc);
-        e = hipGetLastError();
-        aux->tag = state ? 0 : tag;
-        aux->ticket_base = 0;
-        aux->parity = 0;
-    }
-    a.gran = reinterpret_cast<float *>(scratch + head + (state ? 0 : aux->parity) * gran_bytes);
-    a.gran_other = state ? nullptr : reinterpret_cast<float *>(scratch + head + (aux->parity ^ 1u) * gran_bytes);
-    a.ticket_base = aux->ticket_base;
-    if (rh::scan_jump_due()) {  // RH_COUNTER_JUMP: the counter moves on as though launches had taken the tickets in between (the wrap then falls inside this launch)
-        const uint32_t d = (0u - rh::counter_jump().tickets_left) - aux->ticket_base;
-        if (e == hipSuccess) e = rh::counters_add(a.ctl, d, 0, 0, s);
-        aux->ticket_base += d;
-        a.ticket_base = aux->ticket_base;
-    }
-    if (state) a.state_in = snap;
-    if (e == hipSuccess) {
-        static int occupancy[sizeof(kVariants) / sizeof(kVariants[0])];  // asked once per variant
-        int &per_cu_cached = occupancy[v - kVariants];
-        if (per_cu_cached == 0) {
-            int q = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void *>(v->fn), 64 * (int)NW, 0);
-            per_cu_cached = q < 1 ? 1 : q;
-        }
-        int per_cu = per_cu_cached;
-        if (per_cu * (int)NW > 16) per_cu = 16 / (int)NW > 0 ? 16 / (int)NW : 1;
-        if (const char *w = rh::knob(rh::K_BIQUAD_WGS)) per_cu = atoi(w) > 0 ? atoi(w) : per_cu;
-        uint64_t grid = (uint64_t)rh::g_num_cus * (uint64_t)per_cu;
-        const uint64_t total = tiles64 * n_streams;
-        if (grid > total) grid = total;
-        if (e == hipSuccess) {
-            void *args[] = {&a};
-            e = hipLaunchKernel(reinterpret_cast<const void *>(v->fn), dim3((uint32_t)grid), dim3(64 * NW), args, 0, s);
-            if (e == hipSuccess && !state) {  // every workgroup takes two tickets ahead and one per tile it works on
-                aux->ticket_base += (uint32_t)(total + 2 * grid);
-                aux->parity ^= 1u;
-            }
-        }
-    }
-    if (e != hipSuccess) aux->tag = 0;
+    auto pre = [&](const ScanScratch &sc) {
+        snap = sc.own(), xlast = snap + n_sc * 4;
+        hipLaunchKernelGGL(k_bq_pre, dim3(sc.pre_wgs(n_sc)), dim3(256), 0, s, sc.ctl(), sc.words(), sc.lay.n_words(), snap, xlast, state, src, frames, stride, channels, (uint32_t)n_sc);
+        if (state) a.state_in = snap;
+        return hipGetLastError();
+    };
+    static int occupancy[sizeof(kVariants) / sizeof(kVariants[0])];  // asked once per variant
+    hipError_t e = scan_launch(s, scratch_hold, rh::scan::kSeedBiquad, channels, n_sc * 6 * sizeof(float), 2 * channels, state != nullptr, a, reinterpret_cast<const void *>(v->fn), 64 * NW,
+                               occupancy[v - kVariants], knob_int(rh::K_BIQUAD_WGS), 0, pre, [&](uint64_t) { return reinterpret_cast<const void *>(v->fn); });
+    // (a failure up to here has cleared the scratch's tag: the next call starts over.  One of k_bq_post alone does not: the scan is enqueued and
+    // leaves the tables in order -- and with a carried state the tag is 0 anyway)
     if (e == hipSuccess && state) {
         hipLaunchKernelGGL(k_bq_post, dim3((unsigned)((n_sc + 255) / 256)), dim3(256), 0, s, state, snap, xlast, dst, frames, stride, channels, (uint32_t)n_sc);
         e = hipGetLastError();

@@ -7,6 +7,7 @@
 #include <cstdio>
 
 #include "../../include/rodio_hip.h"
+#include "rh_scan_launch.h"  // ScratchAux, kSpinLimit
 
 namespace rh {
 
@@ -73,7 +74,7 @@ inline hipError_t fill_now(void *p, int value, size_t bytes) {
 }
 
 // A fill ON a stream, by a kernel of this library (rh_runtime.hip): whatever initialises state that a later kernel reads is
-// ordered the way kernels are (hipMemsetAsync was part of the limiter's wrong-state flake, rh_limit.hip, k_limit_init).
+// ordered the way kernels are (hipMemsetAsync was part of the limiter's wrong-state flake: rh_scan_common.h, scan_scratch_init).
 hipError_t fill_async(void *p, int value, size_t bytes, hipStream_t s);
 // ctl[0] += d_ticket and ctl[32 * (1 + x)] += d_shards for x < n_shards, as a launch on `s` (RH_COUNTER_JUMP)
 hipError_t counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uint32_t d_shards, hipStream_t s);
@@ -86,14 +87,8 @@ hipError_t counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uin
 // library's own streams; a foreign stream's buffer (a few hundred KiB) lives until the process ends.
 // The caller keeps `hold` (taken here) until its last launch that uses the buffer is enqueued: two host threads that launch on
 // the same stream then cannot interleave their initialisation and kernel launches.
-// What the last user of a stream's scratch left behind, for a user that can save itself work when IT was the last one (the scan
-// kernels: hand-off tables that the launch before has already cleared).  Zeroed when the buffer is (re)allocated and by every call
-// that does not ask for it (another user has written over the scratch since).  Read and written under `hold`.
-struct ScratchAux {
-    uint64_t tag;          // who / what shape (0: nobody)
-    uint32_t ticket_base;  // value of the scratch's ticket counter when the next launch starts
-    uint32_t parity;       // which of two tables the next launch works on
-};
+// ScratchAux (rh_scan_launch.h): what the last user of a stream's scratch left behind, for a user that can save itself work when IT was the
+// last one.  Zeroed when the buffer is (re)allocated and by every call that does not ask for it.  Read and written under `hold`.
 hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, std::unique_lock<std::mutex> &hold, ScratchAux **aux = nullptr);
 // device-to-device copy as a launch on `hs` (hipMemcpyAsync DeviceToDevice makes the calling thread wait for the queue ahead of it)
 hipError_t copy_d2d(void *dst, const void *src, size_t bytes, hipStream_t hs);

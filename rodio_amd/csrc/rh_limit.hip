@@ -67,7 +67,6 @@ namespace {
 constexpr float LOG2_10 = 3.32192809488736234787f;
 constexpr float LOG10_2 = 0.301029995663981195214f;
 constexpr int kMaxR = 16, kMaxNW = 16;
-constexpr uint32_t kSpinLimit = 1u << 22;
 constexpr float kNegligible = 0x1p-30f;  // a weight below this no longer moves an f32 state of the same magnitude
 
 struct LimitTabs {      // per-lane / per-predecessor constants, f64 on the host, rounded once; travels as a kernel argument
@@ -86,7 +85,7 @@ struct LimitArgs {
     float *state_out;          // the caller's state, or nullptr
     uint32_t *ctl;             // [0] ticket
     uint32_t *status;          // the library's sticky failure word (rh_async_status)
-    uint32_t spin;             // polls of one hand-off before the tile gives up (kSpinLimit; RH_SCAN_SPIN_LIMIT overrides: tests of the failure path)
+    uint32_t spin;             // polls of one hand-off before the tile gives up (rh::kSpinLimit; RH_SCAN_SPIN_LIMIT overrides: tests of the failure path)
     uint32_t dma_top;          // 1: the next tile's samples are requested at the top of every tile
     uint64_t frames;           // per stream
     uint64_t stride;           // floats between streams
@@ -997,17 +996,12 @@ __global__ __launch_bounds__(64 * (NW + NIO), (NW + NIO >= 4 ? (C * R <= 16 && C
 #undef a
 }
 
-// Everything the launch finds in its scratch, written by ONE kernel of this library in front of it: the control words (ticket
-// counter, status) zeroed, a snapshot of the caller's states (the last tile of a stream rewrites the state while early tiles
-// may still read it), every hand-off word "not yet".  The scratch itself is the stream's own buffer (rh::stream_scratch).
-// Neither hipMallocAsync/hipFreeAsync per call nor hipMemsetAsync: with them ~7 % of short GpuSource chains carried a wrong
-// state into one tile (a zero aggregate or a zeroed state snapshot where the launch had written something else); either
-// change alone lowered the rate, only both removed it (profiles/r02_limit_flake.md).
+// In front of a launch that is not "clean" (rh_scan_launch.h): the scratch as scan_scratch_init leaves it, and a snapshot of the caller's
+// states (the last tile of a stream rewrites the state while early tiles may still read it).
 __global__ void k_limit_init(uint32_t *ctl, float *snap, const float *state, uint32_t n_state, uint32_t *words, uint64_t n_words) {
     const uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (uint64_t)gridDim.x * blockDim.x;
-    if (i0 < 16) ctl[i0] = 0u;
+    scan_scratch_init(ctl, words, n_words, i0, step);
     for (uint64_t i = i0; i < n_state; i += step) snap[i] = state[i];
-    for (uint64_t i = i0; i < n_words; i += step) words[i] = 0xffffffffu;
 }
 
 using LimitFn = void (*)(const LimitArgs);
@@ -1070,44 +1064,23 @@ extern "C" rh_status rh_limit(float *dst, const float *src, uint64_t frames, uin
     const char *force_seq = rh::knob(rh::K_LIMIT_SEQ);  // diagnostics: the reference-order kernel
     if (!aligned || !scannable || (force_seq && force_seq[0] == '1')) return rh::limit_seq_launch(dst, src, frames, channels, n_streams, k5, state, s);
 
-    // Geometry: the LONGEST tile (64 * R * NW frames) that a stream fills at least half of; among equals, more frames per lane.
-    // Long tiles amortise the scans and the look-backs, and a slowly decaying recurrence (100 ms of release) reaches back
-    // over MANY short tiles: measured (profiles/r02_scan_geometry_midsize.txt) 8192-frame tiles win from 64 x 1 Mi frames down to
-    // 256 x 8192 (21 us against 49 us with single-wave tiles), although the short batches then have fewer tiles than the chip
-    // has CUs.  Single-wave tiles are for blocks of a few hundred frames (a pull shim's).
+    // Geometry: rh::scan::pick_variant.  16-wave tiles only on request, the I/O-wave variant only with RH_LIMIT_NIO=1 (measured SLOWER:
+    // DESIGN.md 5.1; kept selectable so that the measurement can be repeated, and tested: tests/test_gpu_limit.py) where its tile fits.
     const LimitVariant *v = nullptr;
-    if (rh::knob(rh::K_LIMIT_R) || rh::knob(rh::K_LIMIT_NW)) {  // tuning aids: the variant closest to the request
-        const int want_R = rh::knob(rh::K_LIMIT_R) ? atoi(rh::knob(rh::K_LIMIT_R)) : 16, want_NW = rh::knob(rh::K_LIMIT_NW) ? atoi(rh::knob(rh::K_LIMIT_NW)) : 8;
-        for (const LimitVariant &c : kVariants) {
-            if (c.C != (int)channels || c.NIO) continue;
-            auto score = [&](const LimitVariant &x) { return 10 * std::abs(x.NW - want_NW) + std::abs(x.R - want_R); };
-            if (!v || score(c) < score(*v)) v = &c;
-        }
+    if (rh::knob(rh::K_LIMIT_R) || rh::knob(rh::K_LIMIT_NW)) {  // tuning aids
+        const rh::scan::Request want{rh::knob(rh::K_LIMIT_R) ? atoi(rh::knob(rh::K_LIMIT_R)) : 16, rh::knob(rh::K_LIMIT_NW) ? atoi(rh::knob(rh::K_LIMIT_NW)) : 8};
+        v = rh::scan::pick_variant(kVariants, channels, frames, &want, [](const LimitVariant &c) { return !c.NIO; });
     } else {
-        auto tile_of = [](const LimitVariant &x) { return (uint64_t)64 * x.R * x.NW; };
         const char *nio_knob = rh::knob(rh::K_LIMIT_NIO);
-        const bool want_io = nio_knob && nio_knob[0] == '1';  // RH_LIMIT_NIO=1: the I/O-wave variant (measured SLOWER: DESIGN.md 5.1; kept selectable so that the
-        for (const LimitVariant &c : kVariants) {             // measurement can be repeated, and tested: tests/test_gpu_limit.py)
-            if (want_io && c.NIO && c.C == (int)channels && tile_of(c) <= 2 * frames) v = &c;
-        }
-        for (const LimitVariant &c : kVariants) {
-            if (v && v->NIO) break;
-            if (c.C != (int)channels || c.NW > 8 || c.NIO) continue;  // (16-wave tiles: only on request)
-            if (!v) {
-                v = &c;
-                continue;
-            }
-            const bool fits_c = tile_of(c) <= 2 * frames, fits_v = tile_of(*v) <= 2 * frames;
-            const bool better = fits_c != fits_v ? fits_c
-                                : (fits_c ? (tile_of(c) > tile_of(*v) || (tile_of(c) == tile_of(*v) && c.R > v->R))   // the longest that fits
-                                          : tile_of(c) < tile_of(*v));                                                // nothing fits: the shortest
-            if (better) v = &c;
-        }
+        if (nio_knob && nio_knob[0] == '1')
+            for (const LimitVariant &c : kVariants)
+                if (c.NIO && c.C == (int)channels && (uint64_t)64 * c.R * c.NW <= 2 * frames) v = &c;
+        if (!v) v = rh::scan::pick_variant(kVariants, channels, frames, nullptr, [](const LimitVariant &c) { return !c.NIO && c.NW <= 8; });
     }
     if (!v) return RH_ERR_UNSUPPORTED;
     const uint32_t R = (uint32_t)v->R, NW = (uint32_t)v->NW, L = 64u * R, LW = L * NW;
     const uint64_t tiles64 = (frames + LW - 1) / LW;
-    if (tiles64 > 0x7fffffffull || tiles64 * n_streams >= 0xfff00000ull) return RH_ERR_UNSUPPORTED;  // tickets are 32-bit
+    if (!rh::scan::tickets_fit(tiles64, n_streams)) return RH_ERR_UNSUPPORTED;
 
     LimitArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1178,76 +1151,23 @@ extern "C" rh_status rh_limit(float *dst, const float *src, uint64_t frames, uin
         a.t = c.t;
     }
 
-    // scratch: control words + the carried-in states + TWO hand-off tables.  A launch works on one of them and sets the other one's
-    // records back to "not yet" as its tiles finish, so the next launch of the same shape on this stream finds its table clean and its
-    // ticket counter where the host knows it to be: no kernel in front of it (k_limit_init and its boundary were 5 % of a 0.27 ms call).
-    // The first launch of a shape, a launch with a carried state (its snapshot is a kernel anyway) and a launch behind another user of
-    // the stream's scratch (rh::ScratchAux) initialise both tables.
+    // the scratch's head: the carried-in states, snapshot by k_limit_init (a carried state always has that kernel in front)
     const size_t n_state = (size_t)n_streams * channels * 2;
-    const size_t gran_bytes = (((size_t)n_streams * tiles64 * rec_stride(channels) * sizeof(float)) + 63) & ~size_t(63);
-    const size_t head = 64 + ((n_state * 4 + 63) & ~size_t(63));
-    unsigned char *scratch = nullptr;
     std::unique_lock<std::mutex> scratch_hold;
-    rh::ScratchAux *aux = nullptr;
-    RH_HIP_TRY(rh::stream_scratch(s, head + 2 * gran_bytes, reinterpret_cast<void **>(&scratch), scratch_hold, &aux));
-    uint64_t tag = 0x4c494d4954ull;  // "LIMIT", then the shape (FNV-1a)
-    for (uint64_t v : {(uint64_t)n_streams, tiles64, (uint64_t)channels, (uint64_t)head, (uint64_t)gran_bytes, (uint64_t)reinterpret_cast<uintptr_t>(scratch)}) tag = (tag ^ v) * 0x100000001b3ull;
-    tag |= 1;  // (never 0)
-    const char *init_knob = rh::knob(rh::K_LIMIT_INIT);
-    const bool clean = !state && aux->tag == tag && !(init_knob && init_knob[0] == '1');
-    a.ctl = reinterpret_cast<uint32_t *>(scratch);
-    a.status = rh::g_async_status;
-    a.dma_top = rh::knob(rh::K_SCAN_DMA_TOP) ? (uint32_t)atoi(rh::knob(rh::K_SCAN_DMA_TOP)) : 1u;  // measured: 0.312 -> 0.286 ms (limiter), 0.234 -> 0.221 ms (biquad), 64 x 1 Mi frames
-    a.spin = rh::knob(rh::K_SCAN_SPIN_LIMIT) ? (uint32_t)strtoul(rh::knob(rh::K_SCAN_SPIN_LIMIT), nullptr, 10) : kSpinLimit;
-    float *snap = reinterpret_cast<float *>(scratch + 64);
-    hipError_t e = hipSuccess;
-    if (!clean) {
-        const uint64_t n_words = 2 * gran_bytes / 4;
-        const unsigned init_wgs = (unsigned)std::min<uint64_t>(1024, (std::max<uint64_t>(n_words, n_state) + 255) / 256);
-        hipLaunchKernelGGL(k_limit_init, dim3(init_wgs), dim3(256), 0, s, a.ctl, snap, state, state ? (uint32_t)n_state : 0u, reinterpret_cast<uint32_t *>(scratch + head), n_words);
-        e = hipGetLastError();
-        aux->tag = state ? 0 : tag;
-        aux->ticket_base = 0;
-        aux->parity = 0;
-    }
-    a.gran = reinterpret_cast<float *>(scratch + head + (state ? 0 : aux->parity) * gran_bytes);
-    a.gran_other = state ? nullptr : reinterpret_cast<float *>(scratch + head + (aux->parity ^ 1u) * gran_bytes);
-    a.ticket_base = aux->ticket_base;
-    if (rh::scan_jump_due()) {  // RH_COUNTER_JUMP: the counter moves on as though launches had taken the tickets in between (the wrap then falls inside this launch)
-        const uint32_t d = (0u - rh::counter_jump().tickets_left) - aux->ticket_base;
-        if (e == hipSuccess) e = rh::counters_add(a.ctl, d, 0, 0, s);
-        aux->ticket_base += d;
-        a.ticket_base = aux->ticket_base;
-    }
-    if (state) a.state_in = snap, a.state_out = state;
-    if (e == hipSuccess) {
-        static int occupancy[sizeof(kVariants) / sizeof(kVariants[0])];  // asked once per variant (both instantiations share registers and LDS)
-        int &per_cu_cached = occupancy[v - kVariants];
-        if (per_cu_cached == 0) {
-            int q = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, reinterpret_cast<const void *>(v->fn), 64 * (int)(NW + v->NIO), 0);
-            per_cu_cached = q < 1 ? 1 : q;
-        }
-        int per_cu = per_cu_cached;
-        if (per_cu * (int)(NW + v->NIO) > 16) per_cu = 16 / (int)(NW + v->NIO) > 0 ? 16 / (int)(NW + v->NIO) : 1;
-        if (const char *w = rh::knob(rh::K_LIMIT_WGS)) per_cu = atoi(w) > 0 ? atoi(w) : per_cu;  // tuning aid: resident workgroups per CU
-        uint64_t grid = (uint64_t)rh::g_num_cus * (uint64_t)per_cu;
-        const uint64_t total = tiles64 * n_streams;
-        if (grid > total) grid = total;
-        if (const char *g = rh::knob(rh::K_LIMIT_GRID)) grid = atoi(g) > 0 ? (uint64_t)atoi(g) : grid;  // diagnostics
-        if (e == hipSuccess) {
-            void *args[] = {&a};
-            bool skew = v->fn_skew && grid < n_streams;  // see k_limit_scan: only with more streams than workgroups
-            if (const char *k = rh::knob(rh::K_LIMIT_SKEW)) skew = v->fn_skew && k[0] == '1';  // tuning aid
-            e = hipLaunchKernel(reinterpret_cast<const void *>(skew ? v->fn_skew : v->fn), dim3((uint32_t)grid), dim3(64 * (NW + (uint32_t)v->NIO)), args, 0, s);
-            if (e == hipSuccess && !state) {  // every workgroup takes two tickets ahead and one per tile it works on
-                aux->ticket_base += (uint32_t)(total + 2 * grid);
-                aux->parity ^= 1u;
-            }
-        }
-    }
+    auto pre = [&](const ScanScratch &sc) {
+        hipLaunchKernelGGL(k_limit_init, dim3(sc.pre_wgs(n_state)), dim3(256), 0, s, sc.ctl(), sc.own(), state, state ? (uint32_t)n_state : 0u, sc.words(), sc.lay.n_words());
+        if (state) a.state_in = sc.own(), a.state_out = state;
+        return hipGetLastError();
+    };
+    auto kernel_for = [&](uint64_t grid) {
+        bool skew = v->fn_skew && grid < n_streams;  // see k_limit_scan: only with more streams than workgroups
+        if (const char *k = rh::knob(rh::K_LIMIT_SKEW)) skew = v->fn_skew && k[0] == '1';  // tuning aid
+        return reinterpret_cast<const void *>(skew ? v->fn_skew : v->fn);
+    };
+    static int occupancy[sizeof(kVariants) / sizeof(kVariants[0])];  // asked once per variant (both instantiations share registers and LDS)
+    const hipError_t e = scan_launch(s, scratch_hold, rh::scan::kSeedLimit, channels, n_state * sizeof(float), rec_stride(channels), state != nullptr, a, reinterpret_cast<const void *>(v->fn),
+                                     64 * (NW + (uint32_t)v->NIO), occupancy[v - kVariants], knob_int(rh::K_LIMIT_WGS), knob_int(rh::K_LIMIT_GRID), pre, kernel_for);
     if (e != hipSuccess) {
-        aux->tag = 0;  // (whatever state the tables are in: the next call starts over)
         rh::set_hip_error(e, "rh_limit launch");
         return RH_ERR_HIP;
     }

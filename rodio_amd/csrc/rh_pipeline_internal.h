@@ -33,8 +33,7 @@ namespace rhp {
 constexpr int kMaxR = 20;
 constexpr int kGroupLag = RH_CARRY_DEFER;  // a source group's carries are fetched kGroupLag groups (of 8 sources) after its own
 constexpr int kMaxLook = 32;              // 2 lanes x 16 B of LDS-DMA per predecessor tile: 64 lanes
-constexpr uint32_t kSpinLimit = 1u << 22;  // x (~1 us load + s_sleep): seconds, then give up for good.  Waits end by construction (a tile only
-                                           // waits for tiles with earlier tickets); the bound must outlast a GPU that is time-sliced with other processes
+using rh::kSpinLimit;  // polls of one hand-off before a tile gives up for good (rh_scan_launch.h)
 
 struct SrcDesc {          // 32 bytes, read with s_load (constant address space)
     const float *data;

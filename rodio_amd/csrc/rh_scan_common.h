@@ -1,6 +1,7 @@
 // rh_scan_common.h -- device helpers shared by the time-parallel scan kernels (rh_limit.hip, rh_biquad_scan.hip):
 // DPP cross-lane moves, wave reductions, the f32 hand-off words with their 0xFF "not yet" pattern, the swizzled LDS
-// tile image and its LDS-DMA fetch.  gfx950 only; include inside an anonymous namespace of a .hip file.
+// tile image and its LDS-DMA fetch; at the end the host's side of a launch: scan_launch() over the protocol of rh_scan_launch.h.
+// gfx950 only; include inside an anonymous namespace of a .hip file.
 #pragma once
 #include <type_traits>
 
@@ -78,6 +79,15 @@ __device__ __forceinline__ bool word_ok(float v) { return __float_as_uint(v) != 
 __device__ __forceinline__ void word_store(float *p, float v) {
     v = v != v ? __uint_as_float(0x7fc00000u) : v;  // a NaN travels in canonical form, never as the sentinel
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// What a launch that is not "clean" (rh_scan_launch.h) finds in its scratch, written by ONE kernel of this library in front of it -- the
+// unit's own, which also takes its snapshots: the control words (ticket counter, status) zeroed, every hand-off word of both tables "not
+// yet".  Thread i0 of `step`.  Neither hipMallocAsync/hipFreeAsync per call nor hipMemsetAsync: with them ~7 % of short GpuSource chains
+// carried a wrong state into one tile (a zero aggregate or a zeroed state snapshot where the launch had written something else); either
+// change alone lowered the rate, only both removed it (profiles/archive/r02_limit_flake.md).
+__device__ __forceinline__ void scan_scratch_init(uint32_t *ctl, uint32_t *words, uint64_t n_words, uint64_t i0, uint64_t step) {
+    if (i0 < 16) ctl[i0] = 0u;
+    for (uint64_t i = i0; i < n_words; i += step) words[i] = kNotYet;
 }
 typedef float v2f_ __attribute__((ext_vector_type(2)));
 typedef float v4f_ __attribute__((ext_vector_type(4)));
@@ -170,3 +180,66 @@ __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// ---- host: one launch ------------------------------------------------------------------------------------------------------
+// The stream's scratch (rh::stream_scratch) as a launch sees it: rh::scan::Layout at an address
+struct ScanScratch {
+    unsigned char *base;
+    rh::scan::Layout lay;
+    uint32_t *ctl() const { return reinterpret_cast<uint32_t *>(base); }
+    float *own() const { return reinterpret_cast<float *>(base + rh::scan::kOwnOffset); }
+    uint32_t *words() const { return reinterpret_cast<uint32_t *>(base + lay.head); }
+    float *table(uint32_t p) const { return reinterpret_cast<float *>(base + lay.table(p)); }
+    // workgroups of 256 for the unit's pre-kernel: it walks both tables (scan_scratch_init) and n_own items of its own
+    unsigned pre_wgs(uint64_t n_own) const {
+        const uint64_t n = lay.n_words() > n_own ? lay.n_words() : n_own;
+        return (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    }
+};
+inline int knob_int(rh::Knob k) { return rh::knob(k) ? atoi(rh::knob(k)) : 0; }  // 0: unset (or nonsense)
+
+// Everything between a unit's argument block and its kernel on the stream.  `a` (LimitArgs, BqArgs) arrives with n_streams and tiles set
+// (rh::scan::tickets_fit) and leaves with gran, gran_other, ticket_base, ctl, status, spin and dma_top; own_bytes is the unit's head of the
+// scratch, rec_floats a tile's hand-off record.  pre(scratch) enqueues the unit's kernel in front of the launch (scan_scratch_init + its own
+// snapshots) and is called only when that kernel is due -- always with a carried state.  fn stands for the variant in the occupancy query
+// (asked once: `occupancy` is the caller's slot for this variant, 0 at first), kernel_for(grid) is what runs; wgs_knob / grid_knob: workgroups
+// per CU and grid on request, 0 otherwise.  The caller keeps `hold` until its last launch that uses the scratch is enqueued.
+// No std::function, no allocation: a pull shim calls this once per block.
+template <class Args, class Pre, class KernelFor>
+hipError_t scan_launch(hipStream_t s, std::unique_lock<std::mutex> &hold, uint64_t seed, uint32_t channels, size_t own_bytes, size_t rec_floats, bool carried_state, Args &a,
+                       const void *fn, uint32_t block, int &occupancy, int wgs_knob, int grid_knob, Pre pre, KernelFor kernel_for) {
+    namespace scan = rh::scan;
+    const uint64_t total = (uint64_t)a.tiles * a.n_streams;
+    ScanScratch sc{nullptr, scan::layout(own_bytes, (size_t)total * rec_floats * sizeof(float))};
+    rh::ScratchAux *aux = nullptr;
+    hipError_t e = rh::stream_scratch(s, sc.lay.total(), reinterpret_cast<void **>(&sc.base), hold, &aux);
+    if (e != hipSuccess) return e;
+    const char *init_knob = rh::knob(rh::K_LIMIT_INIT);  // RH_LIMIT_INIT=1: both scan kernels initialise their tables in front of every launch
+    const uint64_t tag = scan::shape_tag(seed, a.n_streams, a.tiles, channels, sc.lay, (uint64_t)reinterpret_cast<uintptr_t>(sc.base));
+    const scan::Begin b = scan::begin(aux, tag, carried_state, init_knob && init_knob[0] == '1');
+    a.ctl = sc.ctl();
+    a.status = rh::g_async_status;
+    a.dma_top = rh::knob(rh::K_SCAN_DMA_TOP) ? (uint32_t)atoi(rh::knob(rh::K_SCAN_DMA_TOP)) : 1u;  // measured: 0.312 -> 0.286 ms (limiter), 0.234 -> 0.221 ms (biquad), 64 x 1 Mi frames
+    a.spin = rh::knob(rh::K_SCAN_SPIN_LIMIT) ? (uint32_t)strtoul(rh::knob(rh::K_SCAN_SPIN_LIMIT), nullptr, 10) : rh::kSpinLimit;
+    a.gran = sc.table(b.table);
+    a.gran_other = b.other < 0 ? nullptr : sc.table((uint32_t)b.other);
+    if (b.init) e = pre(sc);
+    if (rh::scan_jump_due()) {  // RH_COUNTER_JUMP
+        const uint32_t d = scan::jump(aux, rh::counter_jump().tickets_left);
+        if (e == hipSuccess) e = rh::counters_add(a.ctl, d, 0, 0, s);
+    }
+    a.ticket_base = aux->ticket_base;
+    if (e == hipSuccess && occupancy == 0) {
+        int q = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, fn, (int)block, 0);
+        occupancy = q < 1 ? 1 : q;
+    }
+    if (e == hipSuccess) {
+        uint64_t grid = scan::launch_grid((uint64_t)rh::g_num_cus, scan::per_cu(occupancy, (int)(block / 64), wgs_knob), total);
+        if (grid_knob > 0) grid = (uint64_t)grid_knob;  // diagnostics
+        void *args[] = {&a};
+        e = hipLaunchKernel(kernel_for(grid), dim3((uint32_t)grid), dim3(block), args, 0, s);
+        if (e == hipSuccess) scan::launched(aux, carried_state, total, grid);
+    }
+    if (e != hipSuccess) scan::failed(aux);
+    return e;
+}

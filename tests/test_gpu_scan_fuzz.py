@@ -113,3 +113,50 @@ def test_biquad_mode1_random_shapes(G, O, case):
         ref = (src.low_pass(freq) if kind == "low_pass" else src.high_pass(freq)).collect()
         assert float(np.max(np.abs(par[s_].cpu().numpy() - ref))) <= TOL, (s_, ch, S, frames, carry, kind, freq)
     G.async_status()
+
+
+def test_launches_without_init_match_forced_init(G):
+    """The kernel in front of a scan launch (k_limit_init, k_bq_pre) is left out behind a launch of the same kernel and shape without a carried
+    state (rodio_amd/csrc/rh_scan_launch.h).  One stream, one sequence that has a kernel three times in a row, a carried state in between, a shape
+    change of one kernel and the other kernel behind it: every result equals, bit for bit, the same call with the initialisation forced
+    (RH_LIMIT_INIT=1).  25 000 frames are four 8192-frame tiles (look-backs across several tiles), 33 000 five: another tag."""
+    import torch
+
+    ch = 2
+    rng = np.random.default_rng(31337)
+    co = G.biquad_coeffs("low_pass", 1000, 0.5, 48000)
+    xb = torch.from_numpy((rng.uniform(-1, 1, (3, 25_000 * ch)) * 0.3).astype(np.float32)).cuda()
+    xl = torch.from_numpy((rng.uniform(-1, 1, (5, 25_000 * ch)) * 1.5).astype(np.float32)).cuda()
+    xl33 = torch.from_numpy((rng.uniform(-1, 1, (5, 33_000 * ch)) * 1.5).astype(np.float32)).cuda()
+    st0 = torch.from_numpy(rng.uniform(-0.2, 0.2, (3, 4 * ch)).astype(np.float32)).cuda()
+
+    def sequence():
+        out = []
+        bq = lambda state=None: out.append(_biquad(G, xb, 25_000, ch, 3, co, 1, state))  # noqa: E731
+        lim = lambda x: out.append(G.limit_batch(x, ch, 48000))  # noqa: E731
+        for _ in range(3):
+            bq()
+        st = st0.clone()
+        bq(st)
+        out.append(st)
+        for _ in range(2):
+            bq()
+        for x in (xl, xl, xl33, xl, xl):
+            lim(x)
+        bq()
+        G.async_status()
+        return [o.cpu().numpy() for o in out]
+
+    with knobs(RH_BIQUAD_NO_FALLBACK="1"):  # the scan kernel or nothing
+        got = sequence()
+    with knobs(RH_BIQUAD_NO_FALLBACK="1", RH_LIMIT_INIT="1"):
+        want = sequence()
+    assert len(got) == len(want) == 13
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert np.isfinite(w).all() and float(np.abs(w).max()) > 0.01, i
+        assert np.array_equal(g.view(np.uint32), w.view(np.uint32)), (i, float(np.max(np.abs(g - w))))
+    # (and the launches of one shape agree among themselves: the tables' rotation does not show)
+    for i in (1, 2, 5, 6, 12):
+        assert np.array_equal(got[i].view(np.uint32), got[0].view(np.uint32)), i
+    for i in (8, 10, 11):
+        assert np.array_equal(got[i].view(np.uint32), got[7].view(np.uint32)), i
