@@ -357,6 +357,34 @@ typedef struct rh_wide_src {
 } rh_wide_src;
 rh_status rh_wide_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
                             const rh_wide_src *srcs_host, uint32_t n_sources, rh_stream stream);
+/* ... with a low_pass / high_pass on any of its sources: mixer.add(src, gain, filter) of a mixer of more than two channels, a block at a
+ * time.  Source s enters the ordered sum as y_s = BltFilter(UniformSourceIterator(Amplify(x_s))) at the mixer's rate and channel count
+ * (mixer.rs:58-66, blt.rs:397-492); an unfiltered one as rh_wide_mix_block takes it.  A filtered source that ends inside the block is
+ * silent behind its last frame (the filter returns None with its input).  The filters travel as three host arrays parallel to srcs_host
+ * (read before the call returns):
+ *   kinds_host    -1: no filter, 0: low_pass, 1: high_pass (which side of THE FILTER CONTRACT below the coefficients are held to)
+ *   coeffs5_host  5 floats a source, {b0,b1,b2,a1,a2} as rh_biquad_coeffs(kind, freq, q, to_rate) gives them (not read where kind is -1)
+ *   states_host   per source a DEVICE pointer to its carried state, 4 * channels floats {x1,x2,y1,y2} per channel (rh_biquad's layout):
+ *                 read at the start of the block, written back at its end.  NULL (the entry or the whole array): zero state, not written back.
+ * mode as for rh_biquad: 0 = the reference's operation order, bit for bit; 1 = the time-parallel scan (<= 1e-5 for a full-scale source)
+ * for the filters inside the contract (rh_filter_scan_ok's rule, applied to the coefficients) and mixes of up to 8 channels, mode 0 for
+ * the rest.  On `stream`, in this order: one launch per 32 filtered sources converts them into rows of the mixer's layout (the bits of
+ * rh_amplify -> rh_uniform_row) and gathers their states; rh_biquad runs over the rows, ONE call per coefficient set for the rows that
+ * span the block (where out_frames * channels is a multiple of 4: the batch form wants rows back to back on 16-byte boundaries; a row
+ * each otherwise) and one per row that ends inside it; rh_wide_mix_block sums the original table with every filtered source replaced by
+ * its row; one launch per 32 carried states writes them back.  Launches per block therefore grow with the number of coefficient sets,
+ * not with the number of filtered sources.  With no filtered source the call IS rh_wide_mix_block.
+ * The rows live in `scratch`, a device buffer of the caller's on a 16-byte boundary, at least
+ * rh_wide_mix_filtered_scratch_bytes(channels, out_frames, number of filtered sources) bytes -- not in the stream's scratch, which
+ * rh_biquad mode 1 claims (and may move) inside the call.  Not needed (NULL) without a filtered source.
+ * RH_ERR_INVALID, nothing written: what rh_wide_mix_block refuses, kinds_host == NULL, a kind outside -1 .. 1, a filtered source without
+ * coefficients, a mode other than 0 / 1, a scratch off its boundary; RH_ERR_CAPACITY: a scratch too small; RH_ERR_UNSUPPORTED: a block
+ * so long that a filtered source's position (phase + j F) leaves 32 bits. */
+rh_status rh_wide_mix_filtered_scratch_bytes(uint32_t channels, uint64_t out_frames, uint32_t n_filtered, uint64_t *bytes);
+rh_status rh_wide_mix_block_filtered(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
+                                     const rh_wide_src *srcs_host, uint32_t n_sources, const int32_t *kinds_host,
+                                     const float *coeffs5_host, float *const *states_host, int32_t mode,
+                                     void *scratch, uint64_t scratch_bytes, rh_stream stream);
 
 /* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
  * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays

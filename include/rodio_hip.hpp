@@ -3137,12 +3137,20 @@ public:
         // Mixers of more than two channels: true = every source a chain of its own, whatever it is (the form of rounds 5; a comparison aid).
         // false (default): a generation of plain continuous sources without filters converts and sums a block in one launch (rh_wide_mix_block)
         bool wide_chains = false;
+        // Mixers of more than two channels: true = a plain continuous source WITH a filter stays in the one-launch generations too -- a block
+        // then runs rh_wide_mix_block_filtered (the filtered sources converted into rows by one launch, rh_biquad over the rows batched by
+        // coefficient set, the carried state per source on the device, and the one mix launch): launches per block no longer grow with the
+        // number of filtered sources.  The entry holds every filter to the contract itself (time-parallel inside it, rodio's operation order
+        // outside it and for mixes of more than 8 channels), so reference_exact_filters has nothing left to decide there.
+        // false (default): such a source is a chain of its own, as before -- the same samples within the contract's 1e-5, other block cuts.
+        bool wide_filters = false;
     };
     /// mixer::mixer(channels, sample_rate) (mixer.rs:25).  One and two channels: the sources are mixed as stereo frames by the fused
     /// kernel, and a mono mixer keeps channel 0 of the mix (ChannelCountConverter(2 -> 1) commutes with the sum: channels.rs:57-85).
     /// MORE than two channels (a 5.1 mix): sources that join together and are all plain continuous ones without a filter (decoded assets,
     /// generators: current_span_len() == None) are converted and summed a block at a time in ONE launch (rh_wide_mix_block: Amplify ->
-    /// SampleRateConverter -> ChannelCountConverter per source and the ordered sum, any rates and layouts side by side).  Anything else --
+    /// SampleRateConverter -> ChannelCountConverter per source and the ordered sum, any rates and layouts side by side; with
+    /// Options::wide_filters a filter on such a source stays in that form too: rh_wide_mix_block_filtered).  Anything else --
     /// a filter, spans, a GpuSource chain -- becomes a chain of its own on the device, [amplify] -> UniformSourceIterator(channels, rate)
     /// -> [its filter] (GpuSource, the blocks staying in device memory), and the mixer adds the chains' blocks in insertion order
     /// (rh_mix_sum): rodio's Mixer::add + MixerSource::next for any layout, bit for bit either way.
@@ -3181,7 +3189,7 @@ public:
             item.filt = filter;
             // ... unless the source is a plain continuous one without a filter: those stay as they are, and a generation of such sources
             // converts and sums a block in ONE launch (rh_wide_mix_block; start_stream_wide decides)
-            item.fusew = !opt_.wide_chains && filter.kind < 0 && !dynamic_cast<GpuSource *>(item.up.get()) && !item.up->current_span_len().has_value() && !ratio_beyond_u32(from, rate_);
+            item.fusew = !opt_.wide_chains && (filter.kind < 0 || opt_.wide_filters) && !dynamic_cast<GpuSource *>(item.up.get()) && !item.up->current_span_len().has_value() && !ratio_beyond_u32(from, rate_);
             if (!item.fusew) make_wide(item);
             if (joins_a_running_mix()) late_join(std::move(item));
             else pending_.push_back(std::move(item));
@@ -3347,6 +3355,8 @@ public:
     }
     /// Blocks of wide generations that ran as one launch (rh_wide_mix_block).
     std::uint64_t wide_fused_blocks() const { return wide_fused_blocks_; }
+    /// ... those of them with a filter on at least one source (Options::wide_filters: rh_wide_mix_block_filtered)
+    std::uint64_t wide_filtered_blocks() const { return wide_filtered_blocks_; }
     /// Output frame (of this mixer) at which the most recently started generation joined.
     std::uint64_t last_join_frame() const { return last_join_; }
     /// Threads that have pulled sources so far (1 until a block was large enough for the pool).
@@ -3550,6 +3560,8 @@ private:
         bool fusew = false;
         std::uint64_t wpos = 0;
         std::uint32_t wF = 1, wT = 1;
+        float wco[5] = {0, 0, 0, 0, 0};       // its filter at the mixer's rate (Options::wide_filters), and the filter's state on the device:
+        std::unique_ptr<detail::DeviceBuf> wstate;  // {x1,x2,y1,y2} per channel of the mix, carried from block to block; freed once the source has played out
         std::shared_ptr<HintTrack> hint;      // size_hint(): see HintTrack
         // a pull of `got` samples (ONE continuous span: the source reports none); `ended`: it returned None behind them
         void note_pull(std::size_t got, bool ended_now) {
@@ -3608,6 +3620,8 @@ private:
         std::uint64_t wm = 0, wend = 0;  // output frames planned so far; (once every source has ended) where the longest stream ends
         std::size_t wrow = 0;            // floats per staged row
         std::vector<rh_wide_src> wtab;   // the block that has been pulled: its sources as the launch sees them,
+        bool wfiltered = false;          // a source of the generation has a filter (Options::wide_filters): its blocks run rh_wide_mix_block_filtered
+        detail::DeviceBuf wscratch;      // ... over rows in this buffer
         std::uint64_t wout = 0;          // its output frames,
         bool wlast = false;              // and whether it is the generation's last
         // where the generation's stream lies in the mixer's and how it ended (enqueue(): the last block of a mix that ends inside a frame)
@@ -3773,6 +3787,12 @@ private:
             if (fused) {
                 const std::uint32_t from = x.up->sample_rate(), gc = std::gcd(from, rate_);
                 x.wF = from / gc, x.wT = rate_ / gc;
+                if (x.filt.kind >= 0) {  // (Options::wide_filters) the filter behind the source's converter, at the mixer's rate: mixer.rs:58-66
+                    check(rh_biquad_coeffs(x.filt.kind, x.filt.freq, x.filt.q, rate_, x.wco), "rh_biquad_coeffs");
+                    x.wstate = std::make_unique<detail::DeviceBuf>(4 * qch_);
+                    check(rh_memset(x.wstate->get(), 0, 4 * qch_ * sizeof(float), stream_), "rh_memset");
+                    g.wfiltered = true;
+                }
             }
         }
         g.srcs = std::move(srcs);
@@ -4000,7 +4020,35 @@ private:
         check(rh_stream_wait_event(stream_, g.copied[g.pslot].get()), "rh_stream_wait_event");
         const std::uint64_t out = g.wout;
         if (out > out_cap_frames_ * 2 - g.fill - g.head) throw Error(RH_ERR_CAPACITY, "GpuMixer: the queue of a wide generation");
-        if (out) {
+        if (out && g.wfiltered) {
+            const std::size_t S = g.srcs.size();
+            std::vector<std::int32_t> kinds(S, -1);
+            std::vector<float> co(5 * S, 0.0f);
+            std::vector<float *> states(S, nullptr);
+            std::uint32_t filtered = 0;
+            for (std::size_t i = 0; i < S; ++i) {
+                Src &x = g.srcs[i];
+                if (x.filt.kind < 0 || !x.wstate) continue;
+                kinds[i] = x.filt.kind;
+                std::copy(x.wco, x.wco + 5, co.begin() + 5 * i);
+                states[i] = x.wstate->get();
+                ++filtered;
+            }
+            std::uint64_t bytes = 0;
+            // (for a whole block even where this one is shorter: the buffer is allocated once per generation)
+            check(rh_wide_mix_filtered_scratch_bytes((std::uint32_t)qch_, std::max<std::uint64_t>(out, opt_.block_frames), filtered, &bytes), "rh_wide_mix_filtered_scratch_bytes");
+            g.wscratch.reset((std::size_t)(bytes / sizeof(float)));
+            check(rh_wide_mix_block_filtered(g.queue_end(), (std::uint32_t)qch_, rate_, out, g.wtab.data(), (std::uint32_t)S, kinds.data(), co.data(), states.data(), 1, g.wscratch.get(),
+                                             g.wscratch.size() * sizeof(float), stream_),
+                  "rh_wide_mix_block_filtered");
+            ++wide_fused_blocks_;
+            if (filtered) ++wide_filtered_blocks_;
+            for (std::size_t i = 0; i < S; ++i)  // a source that has played out leaves: its state goes (it reaches no later block)
+                if (Src &x = g.srcs[i]; x.wstate && x.ended && g.wtab[i].frames < out) {
+                    check(rh_stream_synchronize(stream_), "rh_stream_synchronize");
+                    x.wstate.reset();
+                }
+        } else if (out) {
             check(rh_wide_mix_block(g.queue_end(), (std::uint32_t)qch_, rate_, out, g.wtab.data(), (std::uint32_t)g.wtab.size(), stream_), "rh_wide_mix_block");
             ++wide_fused_blocks_;
         }
@@ -4445,7 +4493,7 @@ private:
     bool device_chains_ = false;     // a chain hands its blocks over on the device: its scan kernels' failure word is read per block
     std::unique_ptr<Reaper> reaper_;
     ChainStats retired_chains_;
-    std::uint64_t wide_fused_blocks_ = 0;
+    std::uint64_t wide_fused_blocks_ = 0, wide_filtered_blocks_ = 0;
     detail::DeviceBuf dout_;         // the mixed block in the mixer's channel layout (channels != 2)
     std::vector<Src> pending_;
     std::vector<std::unique_ptr<Gen>> gens_;

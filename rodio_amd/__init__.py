@@ -66,6 +66,7 @@ from .source import (  # noqa: F401
     wav_probe,
     wav_to_bytes,
     spatial_gains_batch,
+    wide_mix_block_filtered,
 )
 
 __all__ = [n for n in dir() if not n.startswith("_")]

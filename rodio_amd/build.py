@@ -69,6 +69,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     build_noise_test(force, run)
     build_mix_test(force, run)
     build_scan_launch_test(force, run)
+    build_wide_filtered_test(force, run)
     return LIB
 
 
@@ -84,10 +85,37 @@ def build_host_mirror_test(force: bool, run) -> str:
              "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
     # ... and the same driver over tests/cpp/fake_device.cpp (a CPU stand-in for the library: TEST INFRASTRUCTURE, it lets the host logic of the
     # header run in the `-m "not gpu"` suite; nothing of the product links or loads it)
-    fake_src = os.path.join(root, "tests", "cpp", "fake_device.cpp")
+    fakes = _fakes(root)
     fake_exe = os.path.join(root, "tests", "cpp", "host_mirror_test_fake")
-    if force or _stale(fake_exe, [src, fake_src, deps[1], deps[2]]):
-        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", os.path.join(root, "include"), src, fake_src, "-o", fake_exe])
+    if force or _stale(fake_exe, [src, *fakes, deps[1], deps[2]]):
+        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", os.path.join(root, "include"), src, *fakes, "-o", fake_exe])
+    return exe
+
+
+def _fakes(root: str, *more: str):
+    """The CPU stand-ins every *_fake driver links: the header-only mirror names rh_wide_mix_block_filtered (fake_widemix_filtered.cpp) wherever
+    GpuMixer is instantiated, beside the entries of fake_device.cpp."""
+    return [os.path.join(root, "tests", "cpp", f) for f in ("fake_device.cpp", "fake_widemix_filtered.cpp", *more)]
+
+
+def build_wide_filtered_test(force: bool, run) -> str:
+    """tests/cpp/wide_filtered_test.cpp: GpuMixer's filtered wide generations (Options::wide_filters) against the library
+    (wide_filtered_test) and over the CPU stand-ins (wide_filtered_test_fake).  TEST INFRASTRUCTURE: plain g++."""
+    root = os.path.join(HERE, "..")
+    inc = os.path.join(root, "include")
+    src = os.path.join(root, "tests", "cpp", "wide_filtered_test.cpp")
+    exe = os.path.join(root, "tests", "cpp", "wide_filtered_test")
+    if not os.path.exists(src):  # (as build_scan_launch_test: an older suite on this library still builds)
+        return exe
+    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h")]
+    gxx = shutil.which("g++") or "g++"
+    if force or _stale(exe, [src, LIB] + hdrs):
+        run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, src, "-L", HERE, "-lrodio_hip",
+             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
+    fakes = _fakes(root)
+    fexe = os.path.join(root, "tests", "cpp", "wide_filtered_test_fake")
+    if force or _stale(fexe, [src, *fakes] + hdrs):
+        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, src, *fakes, "-o", fexe])
     return exe
 
 
@@ -103,7 +131,7 @@ def build_live_test(force: bool, run) -> str:
     if force or _stale(exe, [src, LIB] + hdrs):
         run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, src, "-L", HERE, "-lrodio_hip",
              "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
-    fakes = [os.path.join(root, "tests", "cpp", "fake_device.cpp"), os.path.join(root, "tests", "cpp", "fake_live.cpp")]
+    fakes = _fakes(root, "fake_live.cpp")
     fake_exe = os.path.join(root, "tests", "cpp", "live_test_fake")
     if force or _stale(fake_exe, [src] + fakes + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, src, *fakes, "-o", fake_exe])
@@ -127,7 +155,7 @@ def build_generators_test(force: bool, run) -> str:
     if force or _stale(mexe, [msrc, LIB] + hdrs):
         run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
              "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
-    fakes = [os.path.join(root, "tests", "cpp", "fake_device.cpp"), os.path.join(root, "tests", "cpp", "fake_generators.cpp")]
+    fakes = _fakes(root, "fake_generators.cpp")
     fexe = os.path.join(root, "tests", "cpp", "generators_mirror_test_fake")
     if force or _stale(fexe, [msrc] + fakes + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
@@ -147,7 +175,7 @@ def build_noise_test(force: bool, run) -> str:
     if force or _stale(mexe, [msrc, LIB] + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
              "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
-    fakes = [os.path.join(root, "tests", "cpp", "fake_device.cpp"), os.path.join(root, "tests", "cpp", "fake_noise.cpp")]
+    fakes = _fakes(root, "fake_noise.cpp")
     fexe = os.path.join(root, "tests", "cpp", "noise_mirror_test_fake")
     if force or _stale(fexe, [msrc] + fakes + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
@@ -167,7 +195,7 @@ def build_mix_test(force: bool, run) -> str:
     if force or _stale(mexe, [msrc, LIB] + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
              "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
-    fakes = [os.path.join(root, "tests", "cpp", f) for f in ("fake_device.cpp", "fake_generators.cpp", "fake_noise.cpp", "fake_mix.cpp")]
+    fakes = _fakes(root, "fake_generators.cpp", "fake_noise.cpp", "fake_mix.cpp")
     fexe = os.path.join(root, "tests", "cpp", "mix_mirror_test_fake")
     if force or _stale(fexe, [msrc] + fakes + hdrs):
         run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])

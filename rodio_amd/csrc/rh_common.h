@@ -108,6 +108,8 @@ bool lerp_div_fast_ok(uint32_t T);
 inline float lerp_rcp(uint32_t T) { return lerp_div_fast_ok(T) ? 1.0f / (float)T : 0.0f; }
 // rh_wav.hip: ChannelCountConverter straight from sample bytes (PCM or f32 frames), a tile of frames per workgroup; false = not launched
 bool pcm_tile_try(float *dst, const uint8_t *data, uint64_t n_samples, uint64_t frames, uint32_t channels, uint32_t to_channels, int fmt, hipStream_t s);
+// rh_recurrence.hip: rh_filter_scan_ok for coefficients {b0,b1,b2,a1,a2} at hand (kind 0 / 1: the low_pass / high_pass threshold of the contract)
+bool filter_scan_ok_coeffs(int32_t kind, const float coeffs5[5]);
 // rh_pipeline_plan.hip: `s` has been synchronised and is about to go -- fused-pipeline handles whose launches went there are idle now
 // (they record their idle event lazily, on the stream of their last launch: never on a destroyed one).
 void rlm_stream_retired(hipStream_t s);

@@ -412,6 +412,12 @@ rh_status rh_biquad_coeffs(int32_t kind, uint32_t freq, float q, uint32_t sample
 int32_t rh_filter_scan_ok(int32_t kind, uint32_t freq, float q, uint32_t sample_rate) {
     float c[5];
     if (rh_biquad_coeffs(kind, freq, q, sample_rate, c) != RH_OK) return 0;
+    return rh::filter_scan_ok_coeffs(kind, c) ? 1 : 0;
+}
+
+}  // extern "C" (reopened below)
+// ... the same rule for a filter that arrives as coefficients (rh_wide_mix_block_filtered): `kind` names the threshold
+bool rh::filter_scan_ok_coeffs(int32_t kind, const float c[5]) {
     const double a1 = c[3], a2 = c[4], disc = a1 * a1 - 4.0 * a2;
     double r;
     if (disc >= 0.0) {
@@ -420,10 +426,8 @@ int32_t rh_filter_scan_ok(int32_t kind, uint32_t freq, float q, uint32_t sample_
     } else {
         r = sqrt(a2 > 0.0 ? a2 : 0.0);
     }
-    return (1.0 - r) >= (kind == 0 ? 0.0125 : 0.075) ? 1 : 0;
+    return (1.0 - r) >= (kind == 0 ? 0.0125 : 0.075);
 }
-
-}  // extern "C" (reopened below)
 namespace rh {
 rh_status agc_chain_launch(float *dst, const float *src, uint64_t n_samples, uint32_t n_streams, const float k5[5], float *state, hipStream_t s);
 rh_status biquad_scan_launch(float *dst, const float *src, uint64_t frames, uint32_t channels, uint32_t n_streams, const float co[5], float *state, hipStream_t s);

@@ -14,6 +14,7 @@
 // and adds: the reference's rounding sequence, bit for bit, with fully coalesced loads and stores.  HBM-bound: every input byte
 // is read once from memory (the second tap of a frame is the first tap of the next: L1 / L2), 4 S C_s N_s bytes in, 4 C M out.
 // The source table travels by value as a kernel argument (32 sources a launch; more continue from the stored partial sum).
+#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -167,6 +168,120 @@ __global__ __launch_bounds__(kBlock) void k_wide_mix_uniform(float *__restrict__
     }
 }
 
+// ---- sources of a launch converted into ROWS instead of a sum (rh_wide_mix_block_filtered: a filter sits between the converter and the mix).
+// k_wide_mix's arithmetic -- Amplify, the lerp in math.rs:25's order with the IEEE division, the verbatim last frame, the pass-through
+// for F == T, channels.rs:59-70 -- stored per source: one lane per output sample of the rows of ONE GROUP of kWideGroup sources (blockIdx.y),
+// whose tap loads leave together; a wave's store to a row is 256 contiguous bytes.  A source that reaches fewer frames than the block
+// writes only those.  The first workgroup of a group also copies its sources' carried filter states (4 floats a channel; NULL: zeros)
+// to where the filter's batches expect them side by side.
+struct WideRowDesc {
+    const float *data;   // as WideDesc::data
+    float *row;          // out_frames x to_ch floats of the mixer's layout (a slot that pads the table: not written, frames == 0)
+    const float *state;  // the source's carried state, or nullptr
+    float *state_row;    // where the filter reads it (nullptr: no state is carried in this call)
+    uint32_t ch, frames, last, rate;
+    float gain, Tf;
+};
+struct WideRowTable {
+    WideRate r[kWideRates];
+    WideRowDesc d[kWideChunk];
+};
+__global__ __launch_bounds__(kBlock) void k_wide_rows(uint32_t to_ch, uint32_t out_frames, const WideRowTable tbl) {
+    const uint64_t total = (uint64_t)out_frames * to_ch;
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    const uint32_t s0 = blockIdx.y * kWideGroup;
+    {
+        // (k_wide_mix: the table is read through the scalar cache, and the first wave of a CU would miss on its lines one after the other.
+        //  This workgroup reads the rates and its own group's descriptors: a word of each of those lines, all in flight at once.)
+        const uint32_t *w = reinterpret_cast<const uint32_t *>(&tbl);
+        constexpr uint32_t kLines = (sizeof(WideRowTable) + 63) / 64;
+        constexpr uint32_t kMine = (kWideGroup * sizeof(WideRowDesc) + 63) / 64 + 1;  // lines a group's descriptors can touch
+        const uint32_t q0 = (uint32_t)((sizeof(WideRate) * kWideRates + s0 * sizeof(WideRowDesc)) / 64);
+        uint32_t t[kMine + 1], touch = 0;
+        t[kMine] = w[0];
+#pragma unroll
+        for (uint32_t q = 0; q < kMine; ++q) t[q] = w[(q0 + q < kLines ? q0 + q : kLines - 1) * 16u];
+#pragma unroll
+        for (uint32_t q = 0; q <= kMine; ++q) touch |= t[q];
+        asm volatile("" ::"s"(touch));
+    }
+    if (blockIdx.x == 0) {
+#pragma unroll
+        for (int u = 0; u < kWideGroup; ++u) {
+            const WideRowDesc d = tbl.d[s0 + u];
+            if (d.state_row)
+                for (uint32_t t = threadIdx.x; t < 4u * to_ch; t += kBlock) d.state_row[t] = d.state ? d.state[t] : 0.0f;
+        }
+    }
+    for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < total; o += stride) {
+        const uint32_t j = (uint32_t)(o / to_ch);
+        const uint32_t c = (uint32_t)(o - (uint64_t)j * to_ch);
+        uint32_t il[kWideRates];
+        float w[kWideRates];
+#pragma unroll
+        for (uint32_t q = 0; q < kWideRates; ++q) {
+            const uint32_t p = tbl.r[q].r0 + j * tbl.r[q].F;  // (host: fits 32 bits)
+            il[q] = p / tbl.r[q].T;
+            w[q] = (float)(p - il[q] * tbl.r[q].T);
+        }
+        float a[kWideGroup], b[kWideGroup], wv[kWideGroup], Tf[kWideGroup], g[kWideGroup];
+        float *row[kWideGroup];
+        bool reach[kWideGroup], on[kWideGroup], lerp[kWideGroup];
+#pragma unroll
+        for (int u = 0; u < kWideGroup; ++u) {
+            const WideRowDesc d = tbl.d[s0 + u];
+            const uint32_t q = d.rate;
+            const uint32_t i = q == 0 ? il[0] : (q == 1 ? il[1] : (q == 2 ? il[2] : il[3]));
+            wv[u] = q == 0 ? w[0] : (q == 1 ? w[1] : (q == 2 ? w[2] : w[3]));
+            Tf[u] = d.Tf;
+            g[u] = d.gain;
+            row[u] = d.row;
+            const uint32_t k = c < d.ch ? c : 0u;  // channels.rs:59-70, as in k_wide_mix
+            reach[u] = j < d.frames;
+            on[u] = reach[u] && (c < d.ch || (c == 1u && d.ch == 1u));
+            lerp[u] = on[u] && d.Tf != 0.0f && i < d.last;
+            const float *pa = d.data + (on[u] ? (uint64_t)i * d.ch + k : 0ull);
+            a[u] = *pa;
+            b[u] = pa[lerp[u] ? d.ch : 0u];
+        }
+#pragma unroll
+        for (int u = 0; u < kWideGroup; ++u) {
+            const float x = a[u] * g[u];  // Amplify (amplify.rs:64) in front of the converter
+            float v = x;
+            if (lerp[u]) {
+                const float y = b[u] * g[u];
+                v = x + (y - x) * wv[u] / Tf[u];
+            }
+            if (reach[u]) row[u][o] = on[u] ? v : 0.0f;
+        }
+    }
+}
+
+// the carried states back to their sources, behind the filters: 4 * to_ch floats each
+struct WideStateTable {
+    const float *from[kWideChunk];
+    float *to[kWideChunk];
+};
+__global__ __launch_bounds__(64) void k_wide_state_out(uint32_t to_ch, const WideStateTable tbl) {
+    const float *from = tbl.from[blockIdx.x];
+    float *to = tbl.to[blockIdx.x];
+    for (uint32_t t = threadIdx.x; t < 4u * to_ch; t += 64) to[t] = from[t];
+}
+
+// What rh_wide_mix_block checks of a table before its first launch: the same answers, for an entry that launches in front of it.
+// fit: the output frames a launch may cover before a source's position r0 + j F leaves 32 bits.
+rh_status wide_check_src(const rh_wide_src &x, uint32_t to_rate, uint64_t out_frames, uint32_t *F, uint32_t *T, uint64_t *fit) {
+    if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
+    const uint32_t g = std::gcd(x.from_rate, to_rate);
+    *F = x.from_rate / g, *T = to_rate / g;
+    if ((uint64_t)*F * *T > 0xffffffffull) return RH_ERR_UNSUPPORTED;
+    if (x.phase >= *T) return RH_ERR_INVALID;
+    *fit = (0xffffffffull - *T) / *F;
+    return *fit ? RH_OK : RH_ERR_UNSUPPORTED;
+}
+inline uint64_t wide_row_pitch(uint32_t channels, uint64_t out_frames) { return (out_frames * channels + 3) & ~3ull; }
+inline uint64_t wide_filtered_bytes(uint32_t channels, uint64_t out_frames, uint64_t n) { return n * (2 * wide_row_pitch(channels, out_frames) + 4ull * channels) * sizeof(float); }
+
 }  // namespace
 
 rh_status rh_wide_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames, const rh_wide_src *srcs_host, uint32_t n_sources, rh_stream stream) {
@@ -288,6 +403,155 @@ rh_status rh_wide_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uin
         if (k || !cont) launch();  // (no source reaches these frames: the mix is +0.0 there)
         RH_CHECK_LAUNCH();
         j0 += nf;
+    }
+    return RH_OK;
+}
+
+rh_status rh_wide_mix_filtered_scratch_bytes(uint32_t channels, uint64_t out_frames, uint32_t n_filtered, uint64_t *bytes) {
+    if (!bytes || channels == 0 || out_frames > 0x7fffffffull) return RH_ERR_INVALID;
+    *bytes = wide_filtered_bytes(channels, out_frames, n_filtered);
+    return RH_OK;
+}
+
+rh_status rh_wide_mix_block_filtered(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames, const rh_wide_src *srcs_host, uint32_t n_sources, const int32_t *kinds_host,
+                                     const float *coeffs5_host, float *const *states_host, int32_t mode, void *scratch, uint64_t scratch_bytes, rh_stream stream) {
+    RH_REQUIRE_INIT();
+    if (out_frames == 0) return RH_OK;
+    if (!dst || channels == 0 || to_rate == 0 || (n_sources && (!srcs_host || !kinds_host)) || (mode != 0 && mode != 1)) return RH_ERR_INVALID;
+    if (out_frames > 0x7fffffffull) return RH_ERR_UNSUPPORTED;
+    bool any = false;
+    for (uint32_t s = 0; s < n_sources; ++s) {
+        if (kinds_host[s] < -1 || kinds_host[s] > 1 || (kinds_host[s] >= 0 && !coeffs5_host)) return RH_ERR_INVALID;
+        any = any || kinds_host[s] >= 0;
+    }
+    if (!any) return rh_wide_mix_block(dst, channels, to_rate, out_frames, srcs_host, n_sources, stream);
+    // Everything is checked before the first launch: a call that fails has written nothing, neither a sample nor a state.
+    struct Row {
+        uint32_t s, F, T;  // the source, its reduced rates
+        bool whole;        // it spans the block (a row that ends inside it is filtered on its own)
+    };
+    std::vector<Row> rows;  // the filtered sources that reach the block, in insertion order
+    bool carried = false;
+    for (uint32_t s = 0; s < n_sources; ++s) {
+        const rh_wide_src &x = srcs_host[s];
+        if (x.frames == 0) continue;
+        uint32_t F, T;
+        uint64_t fit;
+        const rh_status st = wide_check_src(x, to_rate, out_frames, &F, &T, &fit);
+        if (st != RH_OK) return st;
+        if (kinds_host[s] < 0) continue;
+        if (fit < x.frames) return RH_ERR_UNSUPPORTED;
+        rows.push_back(Row{s, F, T, x.frames == out_frames});
+        carried = carried || (states_host && states_host[s]);
+    }
+    if (rows.empty()) return rh_wide_mix_block(dst, channels, to_rate, out_frames, srcs_host, n_sources, stream);
+    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15u)) return RH_ERR_INVALID;
+    if (scratch_bytes < wide_filtered_bytes(channels, out_frames, rows.size())) return RH_ERR_CAPACITY;
+    // The rows, grouped by coefficient set (sets in order of first appearance; in a set the rows that span the block first): what one
+    // rh_biquad call filters lies back to back.
+    auto co = [&](const Row &r) { return coeffs5_host + 5 * (size_t)r.s; };
+    auto same = [&](const Row &a, const Row &b) { return memcmp(co(a), co(b), 5 * sizeof(float)) == 0 && kinds_host[a.s] == kinds_host[b.s]; };
+    {
+        std::vector<Row> grouped;
+        std::vector<bool> taken(rows.size(), false);
+        for (size_t i = 0; i < rows.size(); ++i) {
+            if (taken[i]) continue;
+            for (int whole = 1; whole >= 0; --whole)
+                for (size_t k = i; k < rows.size(); ++k)
+                    if (!taken[k] && rows[k].whole == (whole == 1) && same(rows[i], rows[k])) grouped.push_back(rows[k]);
+            for (size_t k = i; k < rows.size(); ++k)
+                if (same(rows[i], rows[k])) taken[k] = true;
+        }
+        rows.swap(grouped);
+    }
+    const uint64_t pitch = wide_row_pitch(channels, out_frames);
+    const size_t R = rows.size();
+    float *const conv = static_cast<float *>(scratch), *const filt = conv + R * pitch, *const states = filt + R * pitch;
+    hipStream_t hs = rh::as_stream(stream);
+    // 1. the converter: a launch per 32 rows (or per four different (rate, phase) pairs)
+    {
+        WideRowTable tbl;
+        uint32_t k = 0, nr = 0;
+        auto clear_rates = [&]() {
+            for (uint32_t q = 0; q < kWideRates; ++q) tbl.r[q] = WideRate{0u, 1u, 0u, 1.0f};
+            nr = 0;
+        };
+        clear_rates();
+        auto launch = [&]() {
+            while (k % kWideGroup) tbl.d[k++] = WideRowDesc{tbl.d[0].data, nullptr, nullptr, nullptr, 1u, 0u, 0u, 0u, 0.0f, 0.0f};  // (whole groups: slots that reach no frame)
+            const uint64_t total = out_frames * channels;
+            hipLaunchKernelGGL(k_wide_rows, dim3(rh::grid_for((size_t)total, kBlock, 256u * 16u), k / kWideGroup), dim3(kBlock), 0, hs, channels, (uint32_t)out_frames, tbl);
+            k = 0;
+            clear_rates();
+        };
+        for (size_t i = 0; i < R; ++i) {
+            const rh_wide_src &x = srcs_host[rows[i].s];
+            uint32_t q = 0;
+            while (q < nr && !(tbl.r[q].F == rows[i].F && tbl.r[q].T == rows[i].T && tbl.r[q].r0 == x.phase)) ++q;
+            if (q == nr && nr == kWideRates) {
+                launch();
+                q = 0;
+            }
+            if (q == nr) tbl.r[nr++] = WideRate{rows[i].F, rows[i].T, x.phase, (float)rows[i].T};
+            WideRowDesc &d = tbl.d[k++];
+            d.data = x.data;
+            d.row = conv + i * pitch;
+            d.state = states_host ? states_host[rows[i].s] : nullptr;
+            d.state_row = carried ? states + i * 4 * (size_t)channels : nullptr;
+            d.ch = x.channels;
+            d.frames = (uint32_t)x.frames;
+            d.last = x.last;
+            d.rate = q;
+            d.gain = x.gain;
+            d.Tf = rows[i].F == rows[i].T ? 0.0f : (float)rows[i].T;
+            if (k == kWideChunk) launch();
+        }
+        if (k) launch();
+        RH_CHECK_LAUNCH();
+    }
+    // 2. the filter: a batch per coefficient set where the rows lie back to back on 16-byte boundaries, and the rows that end inside the
+    //    block one by one.  Mode 1 only for what the contract covers; rh_biquad itself continues in mode 0 where its scan kernel declines.
+    for (size_t i = 0; i < R;) {
+        size_t whole = 0, n = 0;
+        while (i + n < R && same(rows[i], rows[i + n])) whole += rows[i + n].whole ? 1 : 0, ++n;
+        const int32_t m = mode == 1 && channels <= 8 && rh::filter_scan_ok_coeffs(kinds_host[rows[i].s], co(rows[i])) ? 1 : 0;
+        const size_t batch = whole && (pitch == out_frames * channels || whole == 1) ? whole : 0;
+        for (size_t k = 0; k < n; k += (k < batch ? batch : 1)) {
+            const uint32_t n_streams = k < batch ? (uint32_t)batch : 1u;
+            const rh_status st = rh_biquad(filt + (i + k) * pitch, conv + (i + k) * pitch, srcs_host[rows[i + k].s].frames, channels, n_streams, co(rows[i]),
+                                           carried ? states + (i + k) * 4 * (size_t)channels : nullptr, m, stream);
+            if (st != RH_OK) return st;
+        }
+        i += n;
+    }
+    // 3. the mix: the caller's table with every filtered source replaced by its row -- the mixer's layout and rate, gain 1: it passes through
+    {
+        std::vector<rh_wide_src> mixed(srcs_host, srcs_host + n_sources);
+        for (size_t i = 0; i < R; ++i) {
+            rh_wide_src &x = mixed[rows[i].s];
+            x.data = filt + i * pitch;
+            x.channels = channels;
+            x.from_rate = to_rate;
+            x.phase = 0;
+            x.last = x.last == 0xffffffffu ? 0xffffffffu : (uint32_t)(x.frames - 1);
+            x.gain = 1.0f;
+        }
+        const rh_status st = rh_wide_mix_block(dst, channels, to_rate, out_frames, mixed.data(), n_sources, stream);
+        if (st != RH_OK) return st;
+    }
+    // 4. the states go back to their sources
+    if (carried) {
+        WideStateTable tbl;
+        uint32_t k = 0;
+        for (size_t i = 0; i < R; ++i) {
+            float *to = states_host[rows[i].s];
+            if (to) tbl.from[k] = states + i * 4 * (size_t)channels, tbl.to[k++] = to;
+            if (k == kWideChunk || (k && i + 1 == R)) {
+                hipLaunchKernelGGL(k_wide_state_out, dim3(k), dim3(64), 0, hs, channels, tbl);
+                k = 0;
+            }
+        }
+        RH_CHECK_LAUNCH();
     }
     return RH_OK;
 }

@@ -606,6 +606,42 @@ def filter_scan_ok(kind, freq, q, fs) -> bool:
     return bool(lib.rh_filter_scan_ok(1 if kind in (1, "high_pass") else 0, int(freq), float(q), int(fs)))
 
 
+def wide_mix_block_filtered(dst, channels, to_rate, out_frames, srcs, filters, mode=1, scratch=None):
+    """rh_wide_mix_block_filtered: a block of a mixer of any channel count whose sources may carry a low_pass / high_pass.
+    srcs: a `_lib.WideSrc` array; filters: per source None or (kind, freq, q[, state]) or (kind, coeffs5[, state]) -- kind 0 / "low_pass",
+    1 / "high_pass", coeffs5 five floats {b0,b1,b2,a1,a2}, state a device tensor of 4 * channels floats carried across blocks (updated in
+    place) or None.  scratch: a float32 device tensor for the rows (allocated here when None)."""
+    _ensure()
+    torch = _t()
+    n = len(srcs)
+    kinds = (C.c_int32 * max(n, 1))()
+    coeffs = np.zeros((max(n, 1), 5), np.float32)
+    states = (C.c_void_p * max(n, 1))()
+    filtered = 0
+    for k, f in enumerate(filters):
+        kinds[k] = -1
+        if f is None:
+            continue
+        filtered += 1
+        kinds[k] = 1 if f[0] in (1, "high_pass") else 0
+        if np.ndim(f[1]) == 0:
+            coeffs[k] = biquad_coeffs(kinds[k], f[1], f[2], to_rate)
+            state = f[3] if len(f) > 3 else None
+        else:
+            coeffs[k] = np.asarray(f[1], np.float32)
+            state = f[2] if len(f) > 2 else None
+        _check_state(state, (4 * channels,), "wide_mix_block_filtered")
+        states[k] = _ptr(state) if state is not None else None
+    need = C.c_uint64(0)
+    check(lib.rh_wide_mix_filtered_scratch_bytes(channels, out_frames, filtered, C.byref(need)), "rh_wide_mix_filtered_scratch_bytes")
+    if scratch is None and need.value:
+        scratch = torch.empty(need.value // 4, device="cuda", dtype=torch.float32)
+    check(lib.rh_wide_mix_block_filtered(_ptr(dst), channels, to_rate, out_frames, srcs, n, kinds, coeffs.ctypes.data_as(_lib.f32p), states, mode,
+                                         _ptr(scratch) if scratch is not None else None, scratch.numel() * 4 if scratch is not None else 0, _stream()),
+          "rh_wide_mix_block_filtered")
+    return dst
+
+
 def delay_samples(ns, rate, ch) -> int:
     return int(lib.rh_delay_samples(ns, rate, ch))
 

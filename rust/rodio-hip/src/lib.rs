@@ -1554,6 +1554,9 @@ impl GpuMixer {
     /// blocks (`GpuMixer::pull_block_widefused` of include/rodio_hip.hpp); this twin still forms every mix in stereo and widens it once
     /// (see `with_channels`), so it never issues one: always 0 here.  INTEGRATION.md section 1 lists the difference.
     pub fn wide_fused_blocks(&self) -> u64 { 0 }
+    /// ... and those among them that went through `rh_wide_mix_block_filtered` (a filter on a source of a wide generation,
+    /// `Options::wide_filters` of the C++ mirror; the entry point is declared in [`ffi`]): for the same reason always 0 here.
+    pub fn wide_filtered_blocks(&self) -> u64 { 0 }
     pub fn last_join_frame(&self) -> u64 { self.last_join }
     /// Threads that pull a block's sources.
     pub fn pull_threads(&self) -> u32 {
