@@ -63,156 +63,68 @@ def build(force: bool = False, verbose: bool = True) -> str:
         list(ex.map(run, jobs))
     if force or jobs or _stale(LIB, objs):
         run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs, "-ldl"])
-    build_host_mirror_test(force, run)
-    build_live_test(force, run)
-    build_generators_test(force, run)
-    build_noise_test(force, run)
-    build_mix_test(force, run)
-    build_scan_launch_test(force, run)
-    build_wide_filtered_test(force, run)
+    for name in DRIVERS:
+        build_driver(name, force, run)
     return LIB
 
 
-def build_host_mirror_test(force: bool, run) -> str:
-    """The C++ host mirror (include/rodio_hip.hpp) is header-only; its test driver is a plain g++ program over
-    the C ABI -- no HIP headers, the way a host application links the library."""
-    root = os.path.join(HERE, "..")
-    src = os.path.join(root, "tests", "cpp", "host_mirror_test.cpp")
-    exe = os.path.join(root, "tests", "cpp", "host_mirror_test")
-    deps = [src, os.path.join(root, "include", "rodio_hip.hpp"), os.path.join(root, "include", "rodio_hip.h"), LIB]
-    if force or _stale(exe, deps):
-        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", os.path.join(root, "include"), src, "-L", HERE, "-lrodio_hip",
-             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
-    # ... and the same driver over tests/cpp/fake_device.cpp (a CPU stand-in for the library: TEST INFRASTRUCTURE, it lets the host logic of the
-    # header run in the `-m "not gpu"` suite; nothing of the product links or loads it)
-    fakes = _fakes(root)
-    fake_exe = os.path.join(root, "tests", "cpp", "host_mirror_test_fake")
-    if force or _stale(fake_exe, [src, *fakes, deps[1], deps[2]]):
-        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", os.path.join(root, "include"), src, *fakes, "-o", fake_exe])
-    return exe
+# The test drivers under tests/cpp (TEST INFRASTRUCTURE: plain g++ programs, nothing of the product links or loads them).  A driver over the C ABI
+# or the header-only C++ mirror (include/rodio_hip.hpp) is built twice: against the library (`lib`: no HIP headers, the way a host application
+# links it) and, as NAME_fake, over the CPU stand-ins tests/cpp/fake_device.cpp + fake_widemix_filtered.cpp + `fakes`, which let the host logic
+# run in the `-m "not gpu"` suite (`fake`).  A driver with neither is a program over headers of csrc alone.
+#   hdrs: headers of csrc the driver includes (the fake build and the csrc-only build get -I csrc);  fpc: -ffp-contract=off on the first build
+#   (the fake build always has it: the stand-ins compute what the kernels compute, unfused)
+DRIVERS = {
+    "host_mirror_test": dict(lib=True, fake=True),
+    "live_test": dict(lib=True, fake=True, fakes=["fake_live.cpp"]),
+    "generators_test": dict(hdrs=["rh_generators.h"], fpc=True),  # the phase walk against brute-force stepping, and the serial f32 phases
+    "generators_mirror_test": dict(lib=True, fake=True, hdrs=["rh_generators.h"], fakes=["fake_generators.cpp"]),
+    "noise_mirror_test": dict(lib=True, fake=True, fpc=True, hdrs=["rh_noise.h"], fakes=["fake_noise.cpp"]),
+    "mix_mirror_test": dict(lib=True, fake=True, fpc=True, hdrs=["rh_noise.h", "rh_generators.h"], fakes=["fake_generators.cpp", "fake_noise.cpp", "fake_mix.cpp"]),
+    "scan_launch_test": dict(hdrs=["rh_scan_launch.h"]),  # the scan kernels' host protocol against a model of the device
+    "wide_filtered_test": dict(lib=True, fake=True),
+    "rlm_launch_test": dict(hdrs=["rh_rlm_launch.h"]),  # the fused path's launch decisions: route, row cut, tickets, stream-block geometry
+}
 
 
-def _fakes(root: str, *more: str):
-    """The CPU stand-ins every *_fake driver links: the header-only mirror names rh_wide_mix_block_filtered (fake_widemix_filtered.cpp) wherever
-    GpuMixer is instantiated, beside the entries of fake_device.cpp."""
-    return [os.path.join(root, "tests", "cpp", f) for f in ("fake_device.cpp", "fake_widemix_filtered.cpp", *more)]
-
-
-def build_wide_filtered_test(force: bool, run) -> str:
-    """tests/cpp/wide_filtered_test.cpp: GpuMixer's filtered wide generations (Options::wide_filters) against the library
-    (wide_filtered_test) and over the CPU stand-ins (wide_filtered_test_fake).  TEST INFRASTRUCTURE: plain g++."""
+def build_driver(name: str, force: bool, run) -> str:
+    """tests/cpp/NAME.cpp -> tests/cpp/NAME [and NAME_fake] by its entry in DRIVERS; returns the first.  The library does not need the drivers: one
+    whose source is missing (an older tests/ run on this library) is skipped."""
+    d = DRIVERS[name]
     root = os.path.join(HERE, "..")
     inc = os.path.join(root, "include")
-    src = os.path.join(root, "tests", "cpp", "wide_filtered_test.cpp")
-    exe = os.path.join(root, "tests", "cpp", "wide_filtered_test")
-    if not os.path.exists(src):  # (as build_scan_launch_test: an older suite on this library still builds)
+    src = os.path.join(root, "tests", "cpp", name + ".cpp")
+    exe = os.path.join(root, "tests", "cpp", name)
+    if not os.path.exists(src):
         return exe
-    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h")]
-    gxx = shutil.which("g++") or "g++"
-    if force or _stale(exe, [src, LIB] + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, src, "-L", HERE, "-lrodio_hip",
-             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
-    fakes = _fakes(root)
-    fexe = os.path.join(root, "tests", "cpp", "wide_filtered_test_fake")
-    if force or _stale(fexe, [src, *fakes] + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, src, *fakes, "-o", fexe])
+    csrc_hdrs = [os.path.join(CSRC, h) for h in d.get("hdrs", [])]
+    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h")] + csrc_hdrs
+    gxx = [shutil.which("g++") or "g++", "-std=c++17", "-O2"]
+    fpc = ["-ffp-contract=off"] if d.get("fpc") else []
+    warn = ["-Wall", "-Wextra"]
+    if d.get("lib"):
+        if force or _stale(exe, [src, LIB] + hdrs):
+            run([*gxx, *fpc, "-pthread", *warn, "-I", inc, src, "-L", HERE, "-lrodio_hip", "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
+    elif force or _stale(exe, [src] + csrc_hdrs):
+        run([*gxx, *fpc, *warn, "-I", CSRC, src, "-o", exe])
+    if d.get("fake"):
+        fakes = [os.path.join(root, "tests", "cpp", f) for f in ("fake_device.cpp", "fake_widemix_filtered.cpp", *d.get("fakes", []))]
+        if force or _stale(exe + "_fake", [src] + fakes + hdrs):
+            run([*gxx, "-ffp-contract=off", "-pthread", *warn, "-I", inc, *(["-I", CSRC] if csrc_hdrs else []), src, *fakes, "-o", exe + "_fake"])
     return exe
 
 
-def build_live_test(force: bool, run) -> str:
-    """tests/cpp/live_test.cpp (chains with adjustable stages and periodic_access) against the library, and against
-    tests/cpp/fake_device.cpp + tests/cpp/fake_live.cpp (TEST INFRASTRUCTURE: the CPU stand-in, for the `-m "not gpu"` suite)."""
-    root = os.path.join(HERE, "..")
-    inc = os.path.join(root, "include")
-    src = os.path.join(root, "tests", "cpp", "live_test.cpp")
-    exe = os.path.join(root, "tests", "cpp", "live_test")
-    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h")]
-    gxx = shutil.which("g++") or "g++"
-    if force or _stale(exe, [src, LIB] + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, src, "-L", HERE, "-lrodio_hip",
-             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe])
-    fakes = _fakes(root, "fake_live.cpp")
-    fake_exe = os.path.join(root, "tests", "cpp", "live_test_fake")
-    if force or _stale(fake_exe, [src] + fakes + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, src, *fakes, "-o", fake_exe])
-    return exe
-
-
-def build_generators_test(force: bool, run) -> str:
-    """tests/cpp/generators_test.cpp: the host build of the phase walk (csrc/rh_generators.h) against brute-force stepping, and the
-    serial f32 phases the GPU tests compare the generator kernels with (TEST INFRASTRUCTURE: plain g++, no library)."""
-    root = os.path.join(HERE, "..")
-    src = os.path.join(root, "tests", "cpp", "generators_test.cpp")
-    exe = os.path.join(root, "tests", "cpp", "generators_test")
-    if force or _stale(exe, [src, os.path.join(CSRC, "rh_generators.h")]):
-        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-I", CSRC, src, "-o", exe])
-    # the C++ mirror's generators (include/rodio_hip.hpp) against the library, and against the CPU stand-in (fake_device.cpp + fake_generators.cpp)
-    inc = os.path.join(root, "include")
-    msrc = os.path.join(root, "tests", "cpp", "generators_mirror_test.cpp")
-    mexe = os.path.join(root, "tests", "cpp", "generators_mirror_test")
-    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h"), os.path.join(CSRC, "rh_generators.h")]
-    gxx = shutil.which("g++") or "g++"
-    if force or _stale(mexe, [msrc, LIB] + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
-             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
-    fakes = _fakes(root, "fake_generators.cpp")
-    fexe = os.path.join(root, "tests", "cpp", "generators_mirror_test_fake")
-    if force or _stale(fexe, [msrc] + fakes + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
-    return exe
+def build_generators_test(force: bool, run) -> str:  # (the tests ask for these three by name)
+    build_driver("generators_mirror_test", force, run)
+    return build_driver("generators_test", force, run)
 
 
 def build_noise_test(force: bool, run) -> str:
-    """tests/cpp/noise_mirror_test.cpp: the C++ mirror's noise sources (include/rodio_hip.hpp) against the library (noise_mirror_test), and
-    against the CPU stand-in of rh_noise_init / rh_noise_generate (fake_device.cpp + fake_noise.cpp: noise_mirror_test_fake).  TEST
-    INFRASTRUCTURE: plain g++."""
-    root = os.path.join(HERE, "..")
-    inc = os.path.join(root, "include")
-    msrc = os.path.join(root, "tests", "cpp", "noise_mirror_test.cpp")
-    mexe = os.path.join(root, "tests", "cpp", "noise_mirror_test")
-    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h"), os.path.join(CSRC, "rh_noise.h")]
-    gxx = shutil.which("g++") or "g++"
-    if force or _stale(mexe, [msrc, LIB] + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
-             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
-    fakes = _fakes(root, "fake_noise.cpp")
-    fexe = os.path.join(root, "tests", "cpp", "noise_mirror_test_fake")
-    if force or _stale(fexe, [msrc] + fakes + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
-    return mexe
-
-
-def build_mix_test(force: bool, run) -> str:
-    """tests/cpp/mix_mirror_test.cpp: the C++ mirror's Mix and Crossfade (include/rodio_hip.hpp) against the library (mix_mirror_test), and
-    against the CPU stand-ins (fake_device.cpp + fake_generators.cpp + fake_noise.cpp + fake_mix.cpp: mix_mirror_test_fake).  TEST
-    INFRASTRUCTURE: plain g++."""
-    root = os.path.join(HERE, "..")
-    inc = os.path.join(root, "include")
-    msrc = os.path.join(root, "tests", "cpp", "mix_mirror_test.cpp")
-    mexe = os.path.join(root, "tests", "cpp", "mix_mirror_test")
-    hdrs = [os.path.join(inc, "rodio_hip.hpp"), os.path.join(inc, "rodio_hip.h"), os.path.join(CSRC, "rh_noise.h"), os.path.join(CSRC, "rh_generators.h")]
-    gxx = shutil.which("g++") or "g++"
-    if force or _stale(mexe, [msrc, LIB] + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, msrc, "-L", HERE, "-lrodio_hip",
-             "-Wl,-rpath,$ORIGIN/../../rodio_amd", "-Wl,-rpath-link,/opt/rocm/lib", "-o", mexe])
-    fakes = _fakes(root, "fake_generators.cpp", "fake_noise.cpp", "fake_mix.cpp")
-    fexe = os.path.join(root, "tests", "cpp", "mix_mirror_test_fake")
-    if force or _stale(fexe, [msrc] + fakes + hdrs):
-        run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra", "-I", inc, "-I", CSRC, msrc, *fakes, "-o", fexe])
-    return mexe
+    return build_driver("noise_mirror_test", force, run)
 
 
 def build_scan_launch_test(force: bool, run) -> str:
-    """tests/cpp/scan_launch_test.cpp: the scan kernels' host protocol (csrc/rh_scan_launch.h: variant pick, scratch layout, the launch that needs no
-    initialisation in front of it, table rotation, ticket base) against a model of the device (TEST INFRASTRUCTURE: plain g++, no library)."""
-    root = os.path.join(HERE, "..")
-    src = os.path.join(root, "tests", "cpp", "scan_launch_test.cpp")
-    exe = os.path.join(root, "tests", "cpp", "scan_launch_test")
-    if not os.path.exists(src):  # the library does not need the driver: a tree whose tests/ lacks it (an older suite run on this library) still builds
-        return exe
-    if force or _stale(exe, [src, os.path.join(CSRC, "rh_scan_launch.h")]):
-        run([shutil.which("g++") or "g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I", CSRC, src, "-o", exe])
-    return exe
+    return build_driver("scan_launch_test", force, run)
 
 
 if __name__ == "__main__":

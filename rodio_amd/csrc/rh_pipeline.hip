@@ -2661,60 +2661,141 @@ VariantTab variant_tab(TabKind kind, bool mono) {
     }
 }
 
+// The instances of k_rlm_chunk, of its form for several classes in one launch and of the one that walks classes of one geometry itself
+struct ChunkInst {
+    uint32_t C;
+    int R, KV;
+    const void *one, *multi, *classes;  // (nullptr: no such instance)
+};
+#define RH_FN(k) reinterpret_cast<const void *>(&k)
+static const ChunkInst kChunk[] = {
+    {2, 9, 4, RH_FN((k_rlm_chunk<9, 2, 4>)), RH_FN((k_rlm_chunk_multi<9, 2, 4>)), nullptr},
+    {2, 18, 8, RH_FN((k_rlm_chunk<18, 2, 8>)), RH_FN((k_rlm_chunk_multi<18, 2, 8>)), RH_FN((k_rlm_chunk_classes<18, 2, 8>))},
+    {2, 18, 4, RH_FN((k_rlm_chunk<18, 2, 4>)), RH_FN((k_rlm_chunk_multi<18, 2, 4>)), RH_FN((k_rlm_chunk_classes<18, 2, 4>))},
+    {1, 18, 4, RH_FN((k_rlm_chunk<18, 1, 4>)), RH_FN((k_rlm_chunk_multi<18, 1, 4>)), RH_FN((k_rlm_chunk_classes<18, 1, 4>))},
+    {1, 18, 2, RH_FN((k_rlm_chunk<18, 1, 2>)), RH_FN((k_rlm_chunk_multi<18, 1, 2>)), RH_FN((k_rlm_chunk_classes<18, 1, 2>))},
+};
+#undef RH_FN
+static const ChunkInst *chunk_inst(int R, uint32_t channels, int KV) {
+    for (const ChunkInst &c : kChunk)
+        if (c.C == channels && c.R == R && c.KV == KV) return &c;
+    return nullptr;
+}
 const void *chunk_kernel(int R, uint32_t channels, int KV) {
-    if (channels == 2 && R == 9 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk<9, 2, 4>);
-    if (channels == 2 && R == 18 && KV == 8) return reinterpret_cast<const void *>(&k_rlm_chunk<18, 2, 8>);
-    if (channels == 2 && R == 18 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk<18, 2, 4>);
-    if (channels == 1 && R == 18 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk<18, 1, 4>);
-    if (channels == 1 && R == 18 && KV == 2) return reinterpret_cast<const void *>(&k_rlm_chunk<18, 1, 2>);
-    return nullptr;
+    const ChunkInst *c = chunk_inst(R, channels, KV);
+    return c ? c->one : nullptr;
 }
 
-static const void *chunk_multi_kernel(int R, uint32_t channels, int KV) {
-    if (channels == 2 && R == 9 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk_multi<9, 2, 4>);
-    if (channels == 2 && R == 18 && KV == 8) return reinterpret_cast<const void *>(&k_rlm_chunk_multi<18, 2, 8>);
-    if (channels == 2 && R == 18 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk_multi<18, 2, 4>);
-    if (channels == 1 && R == 18 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk_multi<18, 1, 4>);
-    if (channels == 1 && R == 18 && KV == 2) return reinterpret_cast<const void *>(&k_rlm_chunk_multi<18, 1, 2>);
-    return nullptr;
+rh::rlm::RouteIn route_in(const rh_rlm *p, const Plan &pl) {
+    rh::rlm::RouteIn in{};
+    in.plan = &pl == &p->fast ? rh::rlm::kPlanFast : &pl == &p->pair ? rh::rlm::kPlanPair : rh::rlm::kPlanWave;
+    in.filt = p->filt;
+    in.mix_first_on = p->mix_first_on;
+    in.pre_filter = p->pre_filter;
+    in.chunk_ok = p->chunk.ok;
+    in.no_mix_first = rh::knob(rh::K_NO_MIX_FIRST) != nullptr;
+    in.count = in.n_sources = p->n_sources;
+    return in;
 }
 
-static const void *chunk_classes_kernel(int R, uint32_t channels, int KV) {
-    if (channels == 2 && R == 18 && KV == 8) return reinterpret_cast<const void *>(&k_rlm_chunk_classes<18, 2, 8>);
-    if (channels == 2 && R == 18 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk_classes<18, 2, 4>);
-    if (channels == 1 && R == 18 && KV == 4) return reinterpret_cast<const void *>(&k_rlm_chunk_classes<18, 1, 4>);
-    if (channels == 1 && R == 18 && KV == 2) return reinterpret_cast<const void *>(&k_rlm_chunk_classes<18, 1, 2>);
-    return nullptr;
+void params_common(const rh_rlm *p, const StreamArgs &sa, Params &k) {
+    k.ticket = p->d_ctl;
+    k.status = p->d_ctl + 1;
+    k.F = p->F;
+    k.T = p->T;
+    k.qF = p->F / p->T;
+    k.rF = p->F % p->T;
+    k.Tf = (float)p->T;
+    k.rcpT = rh::lerp_rcp(p->T);  // 0: this T did not pass the exhaustive check of the short division (rh_common.h)
+    k.epoch = p->epoch;
+    k.st_mode = sa.mode;
+    k.st_active = sa.active;
+    k.st_m0 = sa.m0;
+    k.st_g0 = sa.g0;
+    k.st_mfirst = sa.mode ? p->st_mfirst : 0;
+    k.st_win = sa.win;
+    k.st_wout = sa.wout;
+}
+
+// The arguments of k_rlm_chunk for the batch that is set: the chunk plan's tables in place of the active plan's
+static void chunk_params(const rh_rlm *p, Params &k, ChunkArgs &ca) {
+    const ChunkPlan &c = p->chunk;
+    k.tabs = c.d_tabs;
+    k.gran = c.d_gran;
+    k.n_tiles = c.n_tiles;
+    k.J = c.J;
+    k.u = c.uni;
+    ca.m_lo = c.d_mlo;
+    ca.halo = c.d_halo;
+    ca.lookT = c.d_look;
+    ca.powM = c.d_pow;
+    ca.uni = c.d_uni;
+    k.direct = (c.direct && p->exclusive) ? 1u : 0u;
+}
+
+// The arguments of a launch of the active plan's kernel over sources [first, first + count)
+static Params launch_params(const rh_rlm *p, const Plan &pl, uint32_t first, uint32_t count, float *dst, uint32_t batch_streams, uint64_t out_stride, const StreamArgs &sa) {
+    Params k;
+    params_common(p, sa, k);
+    k.srcs = p->d_srcs + first;
+    k.tabs = pl.d_tabs;
+    k.out = dst;
+    k.gran = p->d_gran;
+    k.out_frames = p->out_frames;
+    k.chunk_in = sa.mode ? p->st_chunk_in : p->chunk_in;  // a stream knows its spans whatever the block size
+    k.chunk_out = sa.mode ? p->st_chunk_out : p->chunk_out;
+    k.n_sources = count;
+    k.n_tiles = p->n_tiles;
+    k.J = pl.J;
+    k.ticket_base = p->tk.ticket_base;
+    k.direct = 0;
+    k.rag_merge = k.rag_pairs_from = k.rag_pairs_to = 0;
+    k.prof = p->d_prof;
+    k.eq_frames = p->eq_frames;
+    k.batch_streams = batch_streams;
+    k.shards = rh::rlm::batch_shards(batch_streams, rh::knob(rh::K_NO_TICKET_SHARDS) != nullptr);
+    k.shard_base = p->tk.shard_base;
+    k.out_stride = out_stride;
+    k.gran_cols = sa.gran_cols ? sa.gran_cols : p->n_tiles;
+    k.col0 = sa.gran_cols ? 1u : 0u;
+    k.u = pl.uni;
+    return k;
 }
 
 rh_status chunk_launch_classes(rh_rlm *const *classes, float *const *rows, uint64_t row_capacity_frames, uint32_t n, float *dst_sum, rh_stream stream, bool *taken, bool *summed) {
     *taken = false;
     *summed = false;
     if (n < 2 || n > kChunkMultiMax || rh::knob(rh::K_CLASSES_ONE_BY_ONE)) return RH_OK;
-    const void *fn = nullptr;
-    for (uint32_t k = 0; k < n; ++k) {
+    const ChunkInst *inst = nullptr;
+    for (uint32_t k = 0; k < n; ++k) {  // every class a whole k_rlm_chunk run of one instance, or nothing is touched
         const rh_rlm *h = classes[k];
         if (!h || !h->cls.empty() || !h->plan || h->out_frames == 0 || row_capacity_frames < h->out_frames) return RH_OK;
-        if (!h->chunk.ok || !mix_first_applies(h, *h->plan, h->n_sources, false, false)) return RH_OK;
-        const void *f = chunk_multi_kernel(h->chunk.R, h->cfg.channels, h->chunk.KV);
-        if (!f || (fn && f != fn)) return RH_OK;
-        fn = f;
+        if (rh::rlm::route(route_in(h, *h->plan)) != rh::rlm::kChunk) return RH_OK;
+        const ChunkInst *c = chunk_inst(h->chunk.R, h->cfg.channels, h->chunk.KV);
+        if (!c || !c->multi || (inst && c->multi != inst->multi)) return RH_OK;
+        inst = c;
     }
+    RH_REQUIRE_INIT();
+    for (uint32_t k = 0; k < n; ++k)
+        if (!rows[k] || (reinterpret_cast<uintptr_t>(rows[k]) & 15u)) return RH_ERR_INVALID;
+    hipStream_t s = rh::as_stream(stream);
     ChunkMulti m;
     memset(&m, 0, sizeof m);
-    for (uint32_t k = 0; k < n; ++k) {
+    for (uint32_t k = 0; k < n; ++k) {  // this class's arguments behind the others', tiles by ticket
         rh_rlm *h = classes[k];
-        h->collect = &m;
-        const rh_status st = rlm_launch(h, 0, h->n_sources, rows[k], row_capacity_frames, nullptr, stream, 0, 0, StreamArgs{});
-        h->collect = nullptr;
-        if (st != RH_OK) return st;
-        if (m.n != k + 1) return RH_ERR_UNSUPPORTED;  // (the class took another path after all: its launch is queued, the others' tickets are not)
+        rh_status w = pre_launch(h, s);
+        if (w == RH_OK) w = next_epoch(h, s);
+        if (w != RH_OK) return w;
+        m.e[k].p = launch_params(h, *h->plan, 0, h->n_sources, rows[k], 0, 0, StreamArgs{});
+        chunk_params(h, m.e[k].p, m.e[k].q);
+        m.e[k].p.direct = 0;
+        m.first[k + 1] = m.first[k] + rh::rlm::sharded_grid(h->chunk.n_tiles);
     }
+    m.n = n;
     void *args[] = {&m};
-    hipStream_t s = rh::as_stream(stream);
     // Classes of ONE geometry (equal lengths, one rate pair, one chunk size: one table of tile bounds) whose tiles fit the chip at once: a
     // workgroup of two waves per tile walks the classes itself -- one wave loads, the other converts and filters (k_rlm_chunk_classes)
-    const void *fn2 = rh::knob(rh::K_CLASSES_ONE_WAVE) ? nullptr : chunk_classes_kernel(classes[0]->chunk.R, classes[0]->cfg.channels, classes[0]->chunk.KV);
+    const void *fn2 = rh::knob(rh::K_CLASSES_ONE_WAVE) ? nullptr : inst->classes;
     bool same = fn2 != nullptr;
     for (uint32_t k = 0; k < n && same; ++k) {
         const rh_rlm *h = classes[k], *h0 = classes[0];
@@ -2726,21 +2807,17 @@ rh_status chunk_launch_classes(rh_rlm *const *classes, float *const *rows, uint6
         same = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn2, 128, 0) == hipSuccess && per_cu >= 1 &&
                (uint64_t)classes[0]->chunk.n_tiles <= (uint64_t)per_cu * (uint64_t)rh::g_num_cus;
     }
-    hipError_t e;
-    if (same) {
-        m.sum_out = dst_sum;
-        e = hipLaunchKernel(fn2, dim3(classes[0]->chunk.n_tiles), dim3(128), args, 0, s);
-        *summed = e == hipSuccess;
-    } else {
-        e = hipLaunchKernel(fn, dim3(m.first[m.n]), dim3(64), args, 0, s);
-        if (e == hipSuccess)
-            for (uint32_t k = 0; k < n; ++k) classes[k]->shard_base += (m.first[k + 1] - m.first[k]) / 8u;  // every counter of a class has handed out this many tickets
-    }
+    if (same) m.sum_out = dst_sum;  // (one workgroup per tile, all resident: no tickets)
+    const hipError_t e = same ? hipLaunchKernel(fn2, dim3(classes[0]->chunk.n_tiles), dim3(128), args, 0, s) : hipLaunchKernel(inst->multi, dim3(m.first[n]), dim3(64), args, 0, s);
     if (e != hipSuccess) {
         rh::set_hip_error(e, "k_rlm_chunk_multi / k_rlm_chunk_classes launch");
         return RH_ERR_HIP;
     }
-    for (uint32_t k = 0; k < n; ++k) mark_launch(classes[k], s);
+    *summed = same;
+    for (uint32_t k = 0; k < n; ++k) {
+        rh::rlm::booked(&classes[k]->tk, same, rh::rlm::kShards, m.first[k + 1] - m.first[k]);
+        mark_launch(classes[k], s);
+    }
     *taken = true;
     return RH_OK;
 }
@@ -2758,16 +2835,111 @@ void launch_state_sum(hipStream_t s, const unsigned long long *gran, const SrcDe
     hipLaunchKernelGGL(k_rlm_state_sum, dim3(1), dim3(256), 0, s, gran, srcs, n_sources, cols, tag, w_out);
 }
 
-// Mix first (k_mix_rows / k_mix_ring in front of a one-source fused launch): one-shot runs of filtered equal-length batches.
-// ... and blocks of a stream that carries ONE summed state (rh_rlm_stream_block; rh_rlm_stream_block_v while its sources run
-// together): the state of the sum is the sum of the states, so the block is summed first and the one mixed row streams through
-// the fused kernel with the stream's state words.  `per_source_states`: streams whose blocks carry a state per source.
-bool mix_first_applies(const rh_rlm *p, const Plan &pl, uint32_t count, bool per_source_states, bool batch) {
-    return &pl == &p->fast && p->filt && p->mix_first_on && !per_source_states && !batch && count >= 2 && !rh::knob(rh::K_NO_MIX_FIRST);
+// The ragged pair.  First half: the stable pairs, summed aggregates into the row behind the `count` per-source rows; second half: the few
+// pairs in which a source is about to end, on top of the first (k_rlm_resid) -- or inside the first kernel (Params::rag_merge; mono: always)
+static rh_status launch_pair(rh_rlm *p, const Plan &pl, Params &k, uint32_t grid, hipStream_t s) {
+    Params k1 = k;
+    k1.gran = p->d_gran + (uint64_t)k.n_sources * p->n_tiles * 4;
+    k1.eq_frames = p->rag_frames;  // the sources that last as long as the mix (one length): the end-of-source handling is theirs
+    void *args[] = {&k}, *args1[] = {&k1};
+#ifdef RH_RAG_NO_SUMF
+    const bool merge = false;
+#else
+    const bool merge = !rh::knob(rh::K_RAG_TWO_KERNELS) || !pl.v->plain;
+#endif
+    k1.rag_merge = merge ? 1u : 0u;
+    k1.rag_pairs_from = p->rag_pairs_from;
+    k1.rag_pairs_to = p->rag_pairs_to;
+    uint32_t lds1 = pl.lds_bytes + 128u;  // (the pair list behind the ring)
+    if (const char *w = rh::knob(rh::K_RAG_RESIDENT)) {  // tuning aid: at most this many tiles of the first half on a CU at once
+        const int want = atoi(w);
+        if (want >= 2 && want < 8) lds1 = std::max(lds1, (kLdsGranules / (uint32_t)want) * kLdsGranule);
+    }
+    const uint32_t grid8 = rh::rlm::sharded_grid(grid);  // tiles by ticket from eight counters (k_rlm_fast)
+    k1.shards = rh::rlm::kShards;
+    hipError_t e1 = hipLaunchKernel(reinterpret_cast<const void *>(pl.v->filt), dim3(grid8), dim3(64), args1, lds1, s);
+    if (e1 == hipSuccess) rh::rlm::booked(&p->tk, false, k1.shards, grid8);
+    if (e1 == hipSuccess && !merge) {
+        e1 = hipLaunchKernel(reinterpret_cast<const void *>(pl.v->plain), dim3(grid), dim3(64), args, 2u * (uint32_t)pl.v->KV * 1024u + 128u /* two stages + the pair list */, s);
+        rh::rlm::booked(&p->tk, false, 1, grid);
+    }
+    if (e1 != hipSuccess) {
+        rh::set_hip_error(e1, "ragged batch launch");
+        return RH_ERR_HIP;
+    }
+    return mark_launch(p, s);
+}
+
+// Mix first in one kernel: every tile sums its aligned chunk of every source, then converts and filters its part of the mix
+static rh_status launch_chunk(rh_rlm *p, Params &k, hipStream_t s) {
+    ChunkArgs ca;
+    chunk_params(p, k, ca);
+    const uint32_t grid = k.direct ? k.n_tiles : rh::rlm::sharded_grid(k.n_tiles);  // by ticket: whole rounds of the eight counters (k_rlm_chunk)
+    void *args[] = {&k, &ca};
+    const hipError_t e = hipLaunchKernel(p->chunk.fn, dim3(grid), dim3(64), args, 0, s);
+    if (e != hipSuccess) {
+        rh::set_hip_error(e, "k_rlm_chunk launch");
+        return RH_ERR_HIP;
+    }
+    rh::rlm::booked(&p->tk, k.direct != 0, rh::rlm::kShards, grid);
+    return mark_launch(p, s);
+}
+
+// Mix first: a filtered batch of equal-length sources -- or a block of a stream on the summed state -- is summed at the input rate
+// (k_mix_rows / k_mix_ring: the one pass over the input; filter_first: then filtered there), and `k` becomes the fused launch that converts
+// and filters that ONE stream
+static rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const StreamArgs &sa, rh_stream stream) {
+    hipStream_t s = rh::as_stream(stream);
+    const uint32_t count = k.n_sources;
+    const uint64_t n_floats = (uint64_t)p->eq_frames * p->cfg.channels;
+    const char *ku = rh::knob(rh::K_MIX_U), *kg = rh::knob(rh::K_MIX_GROUPS);
+    const rh::rlm::RowCut c = rh::rlm::row_cut({n_floats, count, (uint32_t)rh::g_num_cus, pre, sa.mode != 0, (uint64_t)p->cfg.max_in_frames * p->cfg.channels,
+                                                ku ? atoi(ku) : rh::rlm::kUnset, kg ? atoi(kg) : rh::rlm::kUnset});
+    if (c.need > p->mix_floats) {
+        const rh_status w = wait_idle(p);
+        if (w != RH_OK) return w;
+        if (p->d_mix) RH_HIP_TRY(hipFree(p->d_mix));
+        p->d_mix = nullptr;
+        RH_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p->d_mix), c.need * sizeof(float)));
+        p->mix_floats = c.need;
+    }
+    SrcDesc *const ydesc = reinterpret_cast<SrcDesc *>(p->d_mix + rh::rlm::row_cut_desc_offset(p->mix_floats));
+    float *const frow = pre ? p->d_mix + c.row : p->d_mix;  // the row the fused launch reads
+    const uint32_t nf = p->eq_frames, mf = (uint32_t)p->out_frames;
+    if (c.ring >= 3) hipLaunchKernelGGL(k_mix_ring<3>, dim3((uint32_t)c.ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
+    else if (c.ring == 2) hipLaunchKernelGGL(k_mix_ring<2>, dim3((uint32_t)c.ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
+    else if (c.U == 1) hipLaunchKernelGGL(k_mix_rows<1>, dim3(c.wgs, c.groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row, sa.src_off);
+    else if (c.U == 2) hipLaunchKernelGGL(k_mix_rows<2>, dim3(c.wgs, c.groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row, sa.src_off);
+    else hipLaunchKernelGGL(k_mix_rows<4>, dim3(c.wgs, c.groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row, sa.src_off);
+    RH_CHECK_LAUNCH();
+    if (pre) {  // the filter of `src.low_pass(f)`, at from_rate, on the mix (time-parallel: rh_biquad mode 1, zero state)
+        const rh_status fs = rh_biquad(frow, p->d_mix, p->eq_frames, p->cfg.channels, 1, p->pre_coeffs, nullptr, 1, stream);
+        if (fs != RH_OK) return fs;
+    }
+    k.srcs = ydesc;
+    k.n_sources = c.groups;  // (the partial rows, added in order by the fused launch; one row when the list was not cut)
+    // every tile of the one-stream launch resident at once: no tickets (see Params::direct)
+    k.direct = rh::rlm::all_resident(p->exclusive, p->n_tiles, (uint64_t)rh::g_num_cus, pl.resident_per_cu) ? 1u : 0u;
+    return RH_OK;
+}
+
+// The active plan's fused kernel, one workgroup per tile (batch mode: per tile and source)
+static rh_status launch_plain(rh_rlm *p, const Plan &pl, Params &k, uint32_t grid, hipStream_t s) {
+    void *args[] = {&k};
+    // batch mode fills the chip many times over: no residency shaping, the bare LDS request (one source per tile: one stage of the ring,
+    // reused by the output transpose)
+    const uint32_t lds = k.batch_streams ? std::max((uint32_t)pl.v->KV * 1024u, 64u * ((uint32_t)pl.v->R * 8u + 8u)) : p->launch_lds;
+    const hipError_t e = hipLaunchKernel(pl.kernel, dim3(grid), dim3(64), args, lds, s);
+    if (e != hipSuccess) {
+        rh::set_hip_error(e, "k_rlm launch");
+        return RH_ERR_HIP;
+    }
+    rh::rlm::booked(&p->tk, k.direct != 0, k.shards, grid);
+    return mark_launch(p, s);
 }
 
 rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint64_t out_capacity_frames, uint64_t *out_frames, rh_stream stream, uint32_t batch_streams, uint64_t out_stride,
-                            const StreamArgs &sa) {
+                     const StreamArgs &sa) {
     RH_REQUIRE_INIT();
     if (!p) return RH_ERR_INVALID;
     if (!p->cls.empty()) return RH_ERR_UNSUPPORTED;  // per-source filters: whole one-shot runs only (rh_rlm_run)
@@ -2777,194 +2949,32 @@ rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint
     if (!dst || (reinterpret_cast<uintptr_t>(dst) & 15u)) return RH_ERR_INVALID;
     if (out_capacity_frames < p->out_frames) return RH_ERR_CAPACITY;
     hipStream_t s = rh::as_stream(stream);
-    {
-        const rh_status w = pre_launch(p, s);
-        if (w != RH_OK) return w;
-    }
+    rh_status w = pre_launch(p, s);
+    if (w == RH_OK) w = next_epoch(p, s);
+    if (w != RH_OK) return w;
     const Plan &pl = *p->plan;
-    {
-        const rh_status w = next_epoch(p, s);
-        if (w != RH_OK) return w;
-    }
-    Params k;
-    k.srcs = p->d_srcs + first;
-    k.tabs = pl.d_tabs;
-    k.out = dst;
-    k.gran = p->d_gran;
-    k.ticket = p->d_ctl;
-    k.status = p->d_ctl + 1;
-    k.out_frames = p->out_frames;
-    k.chunk_in = sa.mode ? p->st_chunk_in : p->chunk_in;  // a stream knows its spans whatever the block size
-    k.chunk_out = sa.mode ? p->st_chunk_out : p->chunk_out;
-    k.n_sources = count;
-    k.n_tiles = p->n_tiles;
-    k.F = p->F;
-    k.T = p->T;
-    k.qF = p->F / p->T;
-    k.rF = p->F % p->T;
-    k.Tf = (float)p->T;
-    k.rcpT = rh::lerp_rcp(p->T);  // 0: this T did not pass the exhaustive check of the short division (rh_common.h)
-    k.epoch = p->epoch;
-    k.J = pl.J;
-    k.ticket_base = p->ticket_base;
-    k.direct = 0;
-    k.rag_merge = k.rag_pairs_from = k.rag_pairs_to = 0;
-    k.prof = p->d_prof;
-    k.eq_frames = p->eq_frames;
-    k.batch_streams = batch_streams;
-    k.shards = (batch_streams >= 16 && batch_streams % 8 == 0 && !rh::knob(rh::K_NO_TICKET_SHARDS)) ? 8u : 1u;
-    k.shard_base = p->shard_base;
-    k.out_stride = out_stride;
-    k.st_mode = sa.mode;
-    k.st_active = sa.active;
-    k.st_m0 = sa.m0;
-    k.st_g0 = sa.g0;
-    k.st_mfirst = sa.mode ? p->st_mfirst : 0;
-    k.st_win = sa.win;
-    k.st_wout = sa.wout;
-    k.gran_cols = sa.gran_cols ? sa.gran_cols : p->n_tiles;
-    k.col0 = sa.gran_cols ? 1u : 0u;
-    k.u = pl.uni;
-    void *args[] = {&k};
+    Params k = launch_params(p, pl, first, count, dst, batch_streams, out_stride, sa);
     const uint64_t grid = (uint64_t)p->n_tiles * (batch_streams ? batch_streams : 1);
     if (grid > 0x7fffffffull) return RH_ERR_UNSUPPORTED;
-    if (&pl == &p->pair && !sa.mode && !batch_streams) {
-        // first half: the stable pairs, summed aggregates into the row behind the `count` per-source rows; second half:
-        // the few pairs in which a source is about to end, on top of the first (k_rlm_resid)
-        Params k1 = k;
-        k1.gran = p->d_gran + (uint64_t)count * p->n_tiles * 4;
-        k1.eq_frames = p->rag_frames;  // the sources that last as long as the mix (one length): the end-of-source handling is theirs
-        void *args1[] = {&k1};
-#ifdef RH_RAG_NO_SUMF
-        const bool merge = false;
-#else
-        const bool merge = !rh::knob(rh::K_RAG_TWO_KERNELS) || !pl.v->plain;  // the pairs inside the first kernel (Params::rag_merge; mono: always)
-#endif
-        k1.rag_merge = merge ? 1u : 0u;
-        k1.rag_pairs_from = p->rag_pairs_from;
-        k1.rag_pairs_to = p->rag_pairs_to;
-        uint32_t lds1 = pl.lds_bytes + 128u;  // (the pair list behind the ring)
-        if (const char *w = rh::knob(rh::K_RAG_RESIDENT)) {  // tuning aid: at most this many tiles of the first half on a CU at once
-            const int want = atoi(w);
-            if (want >= 2 && want < 8) lds1 = std::max(lds1, (kLdsGranules / (uint32_t)want) * kLdsGranule);
-        }
-        const uint32_t grid8 = ((uint32_t)grid + 7u) & ~7u;  // tiles by ticket from eight counters (k_rlm_fast): whole rounds
-        k1.shards = 8;
-        k1.shard_base = p->shard_base;
-        hipError_t e1 = hipLaunchKernel(reinterpret_cast<const void *>(pl.v->filt), dim3(grid8), dim3(64), args1, lds1, s);
-        if (e1 == hipSuccess) p->shard_base += grid8 / 8u;
-        if (e1 == hipSuccess && !merge) {
-            k.ticket_base = p->ticket_base;
-            e1 = hipLaunchKernel(reinterpret_cast<const void *>(pl.v->plain), dim3((uint32_t)grid), dim3(64), args, 2u * (uint32_t)pl.v->KV * 1024u + 128u /* two stages + the pair list */, s);
-            p->ticket_base += (uint32_t)grid;
-        }
-        if (e1 != hipSuccess) {
-            rh::set_hip_error(e1, "ragged batch launch");
-            return RH_ERR_HIP;
-        }
-        return mark_launch(p, s);
+    rh::rlm::RouteIn in = route_in(p, pl);
+    in.first = first;
+    in.count = count;
+    in.batch_streams = batch_streams;
+    in.st_mode = sa.mode;
+    in.gran_cols = sa.gran_cols;
+    const rh::rlm::Route r = rh::rlm::route(in);
+    switch (r) {
+    case rh::rlm::kPair: return launch_pair(p, pl, k, (uint32_t)grid, s);
+    case rh::rlm::kChunk: return launch_chunk(p, k, s);
+    case rh::rlm::kUnsupported: return RH_ERR_UNSUPPORTED;  // filter_first: one-shot runs of equal-length batches (rodio_hip.h)
+    case rh::rlm::kMixed:
+    case rh::rlm::kMixedFiltered:
+        w = launch_mixed(p, pl, k, r == rh::rlm::kMixedFiltered, sa, stream);
+        if (w != RH_OK) return w;
+        break;
+    default: break;
     }
-    // Mix first: a filtered batch of equal-length sources is summed at the input rate (k_mix_rows: the one pass over the input),
-    // and the fused kernel converts and filters that ONE stream.
-    if (p->chunk.ok && !sa.mode && mix_first_applies(p, pl, count, false, batch_streams != 0) && count == p->n_sources && first == 0) {
-        // mix first in one kernel: every tile sums its aligned chunk of every source, then converts and filters its part of the mix
-        const ChunkPlan &c = p->chunk;
-        k.tabs = c.d_tabs;
-        k.gran = c.d_gran;
-        k.n_tiles = c.n_tiles;
-        k.J = c.J;
-        k.u = c.uni;
-        ChunkArgs ca;
-        ca.m_lo = c.d_mlo;
-        ca.halo = c.d_halo;
-        ca.lookT = c.d_look;
-        ca.powM = c.d_pow;
-        ca.uni = c.d_uni;
-        k.direct = (c.direct && p->exclusive) ? 1u : 0u;
-        if (p->collect) {  // one launch for several classes (chunk_launch_classes): this one's arguments behind the others', tiles by ticket
-            ChunkMulti &m = *static_cast<ChunkMulti *>(p->collect);
-            if (m.n >= kChunkMultiMax) return RH_ERR_UNSUPPORTED;
-            k.direct = 0;
-            const uint32_t g8 = (c.n_tiles + 7u) & ~7u;
-            m.e[m.n].p = k;
-            m.e[m.n].q = ca;
-            m.first[m.n + 1] = m.first[m.n] + g8;
-            m.n += 1;
-            return RH_OK;  // (the ticket counters advance in chunk_launch_classes, if the launch it decides on takes tickets)
-        }
-        const uint32_t cgrid = k.direct ? c.n_tiles : (c.n_tiles + 7u) & ~7u;  // by ticket: whole rounds of the eight counters (k_rlm_chunk)
-        void *cargs[] = {&k, &ca};
-        const hipError_t ce = hipLaunchKernel(c.fn, dim3(cgrid), dim3(64), cargs, 0, s);
-        if (ce != hipSuccess) {
-            rh::set_hip_error(ce, "k_rlm_chunk launch");
-            return RH_ERR_HIP;
-        }
-        if (!k.direct) p->shard_base += cgrid / 8u;  // every counter has handed out this many tickets
-        return mark_launch(p, s);
-    }
-    const bool pre = p->pre_filter;
-    if (pre && (&pl != &p->fast || sa.mode || batch_streams)) return RH_ERR_UNSUPPORTED;  // filter_first: one-shot runs of equal-length batches (rodio_hip.h)
-    if (pre || mix_first_applies(p, pl, count, sa.gran_cols != 0, batch_streams != 0)) {
-        const uint64_t n_floats = (uint64_t)p->eq_frames * p->cfg.channels;
-        const size_t row = (size_t)(((sa.mode ? (uint64_t)p->cfg.max_in_frames * p->cfg.channels : n_floats) + 3) & ~3ull);  // a stream: sized once, for its largest block
-        // how the row is cut: vectors per lane, workgroups, and -- short rows -- groups of sources side by side (see k_mix_rows)
-        constexpr uint32_t kMixGroups = 16;
-        const uint64_t nvec = n_floats / 4;
-        int U = 4;  // measured (256 x 1 Mi stereo frames): 0.410 / 0.409 / 0.342 ms for 1 / 2 / 4 vectors per lane
-        // ... where the row fills the chip.  A stream's block is a short row (64 Ki frames: 128 workgroups at U = 4): fewer vectors per lane, more
-        // workgroups, the same loads in flight per lane (8: the kernel takes 8 / U sources per step)
-        while (U > 1 && (nvec + 256ull * U - 1) / (256ull * U) < 2ull * (uint64_t)rh::g_num_cus) U /= 2;
-        if (const char *u = rh::knob(rh::K_MIX_U)) U = atoi(u);
-        const uint32_t per = 256u * (uint32_t)(U == 1 ? 1 : U == 2 ? 2 : 4);
-        const uint32_t wgs = (uint32_t)std::max<uint64_t>(1, (nvec + per - 1) / per);
-        const uint64_t ring_waves = (nvec + 511) / 512;  // 8 KiB chunks
-        int ring = ring_waves >= 2ull * rh::g_num_cus ? 2 : 0;  // ring depth; 0: the vector-load kernel (short rows: more, smaller pieces)
-        if (const char *u = rh::knob(rh::K_MIX_U)) ring = atoi(u) >= 10 ? atoi(u) - 10 : 0;  // tuning aid: 12 / 13 = ring of 2 / 3 stages, 1 / 2 / 4 = vector loads
-        // short rows: groups of sources side by side until the launch holds two workgroups per CU (every group keeps at least 8 sources: the
-        // kernel's pipeline of descriptor fetches and loads)
-        uint32_t groups = 1;
-        const uint64_t per_cu = rh::knob(rh::K_MIX_GROUPS) ? (uint64_t)std::max(1, atoi(rh::knob(rh::K_MIX_GROUPS))) : 2ull;  // tuning aid: workgroups per CU the cut aims at
-        if (!pre && !ring && !rh::knob(rh::K_MIX_U))
-            while (groups < kMixGroups && (uint64_t)wgs * groups < per_cu * (uint64_t)rh::g_num_cus && count / (groups * 2) >= 8) groups *= 2;
-        // the mixed row (16-byte vectors) [, the filtered row] -- or the groups' partial rows --, then the descriptors (32 bytes each) at the very end
-        const size_t rows_needed = pre ? 2 : (sa.mode ? kMixGroups : groups);  // (a stream: sized once, for whatever its blocks will need)
-        const size_t need = row * rows_needed + 64 + kMixGroups * 8;
-        if (need > p->mix_floats) {
-            const rh_status w = wait_idle(p);
-            if (w != RH_OK) return w;
-            if (p->d_mix) RH_HIP_TRY(hipFree(p->d_mix));
-            p->d_mix = nullptr;
-            RH_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p->d_mix), need * sizeof(float)));
-            p->mix_floats = need;
-        }
-        SrcDesc *const ydesc = reinterpret_cast<SrcDesc *>(p->d_mix + (p->mix_floats - 32 - kMixGroups * 8));
-        float *const frow = pre ? p->d_mix + row : p->d_mix;  // the row the fused launch reads
-        const uint32_t nf = p->eq_frames, mf = (uint32_t)p->out_frames;
-        if (ring >= 3) hipLaunchKernelGGL(k_mix_ring<3>, dim3((uint32_t)ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
-        else if (ring == 2) hipLaunchKernelGGL(k_mix_ring<2>, dim3((uint32_t)ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
-        else if (U == 1) hipLaunchKernelGGL(k_mix_rows<1>, dim3(wgs, groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)row, sa.src_off);
-        else if (U == 2) hipLaunchKernelGGL(k_mix_rows<2>, dim3(wgs, groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)row, sa.src_off);
-        else hipLaunchKernelGGL(k_mix_rows<4>, dim3(wgs, groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)row, sa.src_off);
-        RH_CHECK_LAUNCH();
-        if (pre) {  // the filter of `src.low_pass(f)`, at from_rate, on the mix (time-parallel: rh_biquad mode 1, zero state)
-            const rh_status fs = rh_biquad(frow, p->d_mix, p->eq_frames, p->cfg.channels, 1, p->pre_coeffs, nullptr, 1, stream);
-            if (fs != RH_OK) return fs;
-        }
-        k.srcs = ydesc;
-        k.n_sources = groups;  // (the partial rows, added in order by the fused launch; one row when the list was not cut)
-        // every tile of the one-stream launch resident at once: no tickets (see Params::direct)
-        k.direct = (p->exclusive && (uint64_t)p->n_tiles <= (uint64_t)rh::g_num_cus * (uint64_t)std::max(pl.resident_per_cu, 0)) ? 1u : 0u;
-    }
-    // batch mode fills the chip many times over: no residency shaping, the bare LDS request
-    hipError_t e = hipLaunchKernel(pl.kernel, dim3((uint32_t)grid), dim3(64), args, batch_streams ? std::max((uint32_t)pl.v->KV * 1024u, 64u * ((uint32_t)pl.v->R * 8u + 8u)) /* one source per tile: one stage of the ring, reused by the output transpose */ : p->launch_lds, s);
-    if (e != hipSuccess) {
-        rh::set_hip_error(e, "k_rlm launch");
-        return RH_ERR_HIP;
-    }
-    if (k.direct) {}  // no tickets taken
-    else if (k.shards > 1) p->shard_base += (uint32_t)(grid / k.shards);
-    else p->ticket_base += (uint32_t)grid;  // every launch takes exactly one ticket per workgroup
-    return mark_launch(p, s);
+    return launch_plain(p, pl, k, (uint32_t)grid, s);
 }
 
 }  // namespace rhp

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rh_common.h"
+#include "rh_rlm_launch.h"  // the launch decisions: route, row_cut, Tickets, sblk_geom
 
 namespace rh {
 struct ResampleGeom {
@@ -256,7 +257,6 @@ struct rh_rlm {
     size_t mix_floats = 0;
     ChunkPlan chunk;            // mix first in one kernel (k_rlm_chunk)
     bool cls_one_launch = false;  // per-source filters: the last run walked the classes in one launch (k_rlm_chunk_multi)
-    void *collect = nullptr;    // chunk_launch_classes: the launch being put together (rlm_launch then adds this handle's arguments to it instead of launching)
     void *sblk = nullptr;       // a stream's summed blocks in one kernel (k_rlm_sblk: rh_pipeline_sblk.hip owns the type)
     bool pre_filter = false;    // cfg.filter_first: the filter runs at from_rate in front of the converter (the fused kernels then run without one)
     float pre_coeffs[5] = {1.f, 0.f, 0.f, 0.f, 0.f};
@@ -265,8 +265,7 @@ struct rh_rlm {
     uint64_t out_frames = 0;
     uint32_t epoch = 0;     // the tag of the last launch's words (rhp::next_epoch: 0 < epoch <= kEpochLimit)
     uint32_t n_epochs = 0;  // tags taken (RH_COUNTER_JUMP counts them)
-    uint32_t ticket_base = 0;
-    uint32_t shard_base = 0;  // batch mode with sharded ticket counters (d_ctl + 32*(1+x)): tickets each of them has handed out
+    rh::rlm::Tickets tk;  // where the ticket counters stand (d_ctl; the eight sharded ones: d_ctl + 32*(1+x))
     // block streaming (rh_rlm_stream_*)
     bool st_on = false, st_done = false;
     uint64_t st_g0 = 0, st_m = 0;
@@ -356,7 +355,11 @@ rh_status chunk_launch_classes(rh_rlm *const *classes, float *const *rows, uint6
 void launch_state(hipStream_t s, unsigned long long *gran, const Tables *tabs, uint32_t n_sources, uint32_t cols, uint32_t last_col, uint32_t J, uint32_t epoch, uint32_t next_epoch);
 // k_rlm_state_sum on `s`: the sum of the live sources' states (column 0 of their rows, tagged `tag`) -> the 4 words of a summed state
 void launch_state_sum(hipStream_t s, const unsigned long long *gran, const SrcDesc *srcs, uint32_t n_sources, uint32_t cols, uint32_t tag, float *w_out);
-bool mix_first_applies(const rh_rlm *p, const Plan &pl, uint32_t count, bool per_source_states, bool batch);
+// The facts rh::rlm::route reads, for a whole one-shot run of the handle's sources on plan `pl`; the callers set what differs (first, count,
+// batch_streams, the stream's mode and gran_cols)
+rh::rlm::RouteIn route_in(const rh_rlm *p, const Plan &pl);
+// What every launch of the fused kernels takes from the handle: the control words, the rates, the epoch and the stream's block
+void params_common(const rh_rlm *p, const StreamArgs &sa, Params &k);
 rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint64_t out_capacity_frames, uint64_t *out_frames, rh_stream stream, uint32_t batch_streams, uint64_t out_stride_floats,
                      const StreamArgs &sa = StreamArgs());
 // rh_pipeline_sblk.hip: a block of a stream on the summed state in ONE launch (k_rlm_sblk); *taken = false: not this kernel's block

@@ -80,10 +80,10 @@ rh_status next_epoch(rh_rlm *p, hipStream_t s, bool *launched) {
     const rh::CounterJump &j = rh::counter_jump();
     if (j.on && ++p->n_epochs == j.after) {  // RH_COUNTER_JUMP: every counter of the handle as though the launches in between had run
         const uint32_t to = 0u - j.tickets_left;
-        const uint32_t dt = to - p->ticket_base, ds = to - p->shard_base;
+        const uint32_t dt = to - p->tk.ticket_base, ds = to - p->tk.shard_base;
         RH_HIP_TRY(rh::counters_add(p->d_ctl, dt, 8u, ds, s));
-        p->ticket_base += dt;
-        p->shard_base += ds;
+        p->tk.ticket_base += dt;
+        p->tk.shard_base += ds;
         const uint32_t target = kEpochLimit - (j.launches_left < kEpochLimit - 1 ? j.launches_left : kEpochLimit - 1);
         if (target > p->epoch) {  // the words that wait for the next launch move with the epoch; the older ones keep their (now stale) tags
             const rh_status st = retag_tables(p, s, Retag{p->epoch + 1u, p->epoch + 1u, p->epoch - target, false});
@@ -1094,7 +1094,7 @@ rh_status rh_rlm_geometry(rh_rlm *p, rh_rlm_geometry_info *info) {
     info->n_tiles = p->n_tiles;
     info->general_kernel = (pl.general || p->plan == &p->pair) ? 1u : 0u;
     info->ragged_pair = p->plan == &p->pair ? 1u : 0u;
-    info->mix_first = (p->pre_filter && p->plan == &p->fast) ? 1u : mix_first_applies(p, pl, p->n_sources, false, false) ? (p->chunk.ok ? 2u : 1u) : 0u;
+    info->mix_first = rh::rlm::mix_first_code(rh::rlm::route(route_in(p, pl)));
     return RH_OK;
 }
 

@@ -467,6 +467,7 @@ const Inst kInst[] = {
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 namespace rhp {
 
+static_assert((uint64_t)kSblkH == rh::rlm::kSblkHalo, "sblk_geom cuts the windows for the kernel's halo");
 struct SblkPlan {
     int R = 0;                 // the R the filter tables were built for (0: none yet)
     Uniforms uni;
@@ -520,6 +521,32 @@ void sblk_free(rh_rlm *p) {
     p->sblk = nullptr;
 }
 
+// B^d until the filter has forgotten (||B^d|| < 2^-40: s.Dmax frames), once per handle
+static rh_status sblk_powers(rh_rlm *p, SblkPlan &s) {
+    if (s.d_pow || s.unusable) return RH_OK;
+    const M2 A{-(double)p->coeffs[3], -(double)p->coeffs[4], 1.0, 0.0};
+    M2 Tm, Ti;
+    scan_basis((double)p->coeffs[3], (double)p->coeffs[4], Tm, Ti);
+    const M2 B = mul(mul(Tm, A), Ti);
+    std::vector<float> pw;
+    M2 cur{1, 0, 0, 1};
+    uint32_t d = 0;
+    for (; d <= (1u << 16); ++d) {
+        pw.resize((size_t)(d + 1) * 4);
+        put(&pw[(size_t)d * 4], cur);
+        if (d > 0 && norm(cur) < 0x1p-40) break;
+        cur = mul(cur, B);
+    }
+    if (d > (1u << 16)) {
+        s.unusable = true;
+        return RH_OK;
+    }
+    RH_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_pow), pw.size() * 4));
+    RH_HIP_TRY(hipMemcpy(s.d_pow, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
+    s.Dmax = d;
+    return RH_OK;
+}
+
 static rh_status sblk_tables(rh_rlm *p, SblkPlan &s, int R) {
     if (s.R == R) return RH_OK;
     const rh_status w = wait_idle(p);  // an earlier block may still read the tables
@@ -531,24 +558,6 @@ static rh_status sblk_tables(rh_rlm *p, SblkPlan &s, int R) {
     M2 Tm, Ti;
     scan_basis((double)p->coeffs[3], (double)p->coeffs[4], Tm, Ti);
     const M2 B = mul(mul(Tm, A), Ti);
-    if (!s.d_pow) {  // B^d until the filter has forgotten (||B^d|| < 2^-40), once per handle
-        std::vector<float> pw;
-        M2 cur{1, 0, 0, 1};
-        uint32_t d = 0;
-        for (; d <= (1u << 16); ++d) {
-            pw.resize((size_t)(d + 1) * 4);
-            put(&pw[(size_t)d * 4], cur);
-            if (d > 0 && norm(cur) < 0x1p-40) break;
-            cur = mul(cur, B);
-        }
-        if (d > (1u << 16)) {
-            s.unusable = true;
-            return RH_OK;
-        }
-        RH_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_pow), pw.size() * 4));
-        RH_HIP_TRY(hipMemcpy(s.d_pow, pw.data(), pw.size() * 4, hipMemcpyHostToDevice));
-        s.Dmax = d;
-    }
     Tables *h = new Tables();
     std::memset(h, 0, sizeof(Tables));
     Uniforms &U = s.uni;
@@ -590,58 +599,31 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
     *taken = false;
     const uint32_t C = p->cfg.channels;
     if (!p->filt || (C != 1 && C != 2) || p->st_chunk_in || n_sources < 2 || n_sources > 64u * kSblkWaves || out == 0 || rh::knob(rh::K_NO_SBLK) || rh::knob(rh::K_NO_MIX_FIRST)) return RH_OK;
-    if ((avail * C) % 4 != 0 || avail < 8 || avail >= (1ull << 29)) return RH_OK;
-    const uint64_t F = p->F, T = p->T, H = kSblkH, FB = 4ull * C;
-    if (2 * F > 3 * T) return RH_OK;  // the two frames the filter looks back at start at most 3 input frames in front of a frame's first tap
-    if (sa.m0 + out >= (1ull << 44) || sa.g0 >= (1ull << 40)) return RH_OK;  // (m * F stays inside 64 bits)
-    if ((out + 8) * F + T >= (1ull << 31) || (avail + 8) * T >= (1ull << 31)) return RH_OK;  // (the tiles count in 32 bits, relative to the block)
-    // the input frames the block's output reaches: up to the second tap of its last frame
-    const uint64_t i_last = (uint64_t)(((unsigned __int128)(sa.m0 + out - 1) * F) / T);
-    uint64_t reach = i_last + 2 > sa.g0 ? i_last + 2 - sa.g0 : 1;
-    reach = reach < avail ? reach : avail;
     if (!p->sblk) p->sblk = new SblkPlan();
     SblkPlan &s = *static_cast<SblkPlan *>(p->sblk);
-    if (s.unusable) return RH_OK;
-    // the instance: the smallest window whose tiles fit the chip one per CU (more, smaller tiles would queue behind each other; fewer, larger
-    // ones leave CUs idle); RH_SBLK_KV pins it
-    const bool ovl = p->st_overlap && p->exclusive && !rh::knob(rh::K_SBLK_NO_OVERLAP);  // rh_rlm_stream_overlap (rows resident: the caller's promise)
-    const Inst *pick = nullptr;
-    uint64_t tiles = 0, P = 0;
-    const char *pin = rh::knob(rh::K_SBLK_KV);
-    const Inst *const tab = kInst;
-    const size_t n_tab = sizeof(kInst) / sizeof(kInst[0]);
-    for (size_t ii = 0; ii < n_tab; ++ii) {
-        const Inst &in = tab[ii];
-        if ((uint32_t)in.C != C) continue;
-        if (pin && atoi(pin) != in.KV) continue;
-        const uint64_t Wd = (uint64_t)in.KV * 1024 / FB, Pmax = Wd - H;
-        uint64_t t = (reach > H ? reach - H + Pmax - 1 : Pmax) / Pmax;  // windows of stride Pmax that cover `reach` frames
-        if (t == 0) t = 1;
-        // ... at an even stride (whole 16-byte vectors), so that the tiles are of one size
-        const uint64_t vf = 16 / FB;
-        uint64_t Pe = ((reach > H ? reach - H : 1) + t - 1) / t;
-        Pe = (Pe + vf - 1) / vf * vf;
-        if (Pe > Pmax) Pe = Pmax / vf * vf;
-        if ((Wd * T + F - 1) / F + 3 > 64ull * in.R) continue;  // more output frames in a window than 64 runs hold
-        pick = &in;
-        tiles = t;
-        P = Pe;
-        if (t <= (uint64_t)rh::g_num_cus) break;
+    {
+        const rh_status st = sblk_powers(p, s);
+        if (st != RH_OK) return st;
+        if (s.unusable) return RH_OK;
     }
-    if (!pick || tiles == 0 || tiles > 0x3fffffull) return RH_OK;
+    // every "not this kernel's block" in front of the first thing that touches the handle's launch state (the instance, the windows, the look-back)
+    const char *pin = rh::knob(rh::K_SBLK_KV);
+    rh::rlm::SblkGeom g;
+    if (rh::rlm::sblk_geom(kInst, sizeof(kInst) / sizeof(kInst[0]), {C, p->F, p->T, avail, out, sa.m0, sa.g0, p->st_mfirst, (uint32_t)rh::g_num_cus, pin ? atoi(pin) : rh::rlm::kUnset, s.Dmax}, &g) !=
+        rh::rlm::kSblkYes)
+        return RH_OK;
+    const Inst *const pick = &kInst[g.inst];
+    const uint64_t tiles = g.tiles;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pick->fn, 64 * (kSblkWaves + 1), 0) != hipSuccess || per_cu < 1) return RH_OK;
+    const bool direct = rh::rlm::all_resident(p->exclusive, tiles, (uint64_t)rh::g_num_cus, per_cu);
+    if (rh::rlm::sblk_too_long(direct, tiles, (uint64_t)rh::g_num_cus, per_cu)) return RH_OK;
     {
         const rh_status st = sblk_tables(p, s, pick->R);
         if (st != RH_OK) return st;
-        if (s.unusable || !s.d_tabs) return RH_OK;
+        if (!s.d_tabs) return RH_OK;
     }
-    // J: tiles in front of a tile that the filter has not forgotten (a tile owns at least (P - 1) T / F - 1 frames)
-    const uint64_t n_min = (P - 1) * T / F >= 2 ? (P - 1) * T / F - 1 : 1;
-    const uint64_t J = ((uint64_t)s.Dmax + n_min - 1) / n_min;
-    if (J == 0 || J > 32) return RH_OK;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pick->fn, 64 * (kSblkWaves + 1), 0) != hipSuccess || per_cu < 1) return RH_OK;
-    const bool direct = p->exclusive && tiles <= (uint64_t)rh::g_num_cus * (uint64_t)per_cu;
-    if (!direct && tiles > 8ull * (uint64_t)rh::g_num_cus * (uint64_t)per_cu) return RH_OK;  // (long blocks: the two-launch form reaches the chip's rate there)
+    const bool ovl = p->st_overlap && p->exclusive && !rh::knob(rh::K_SBLK_NO_OVERLAP);  // rh_rlm_stream_overlap (rows resident: the caller's promise)
     if ((size_t)tiles > s.cap_tiles) {
         const rh_status w = wait_idle(p);
         if (w != RH_OK) return w;
@@ -682,57 +664,34 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
     }
     Params k;
     std::memset(&k, 0, sizeof k);
+    params_common(p, sa, k);
     k.srcs = p->d_srcs;
     k.tabs = s.d_tabs;
     k.out = dst;
-    k.gran = nullptr;
-    k.ticket = p->d_ctl;
-    k.status = p->d_ctl + 1;
     k.out_frames = out;
-    k.chunk_in = k.chunk_out = 0;
     k.n_sources = n_sources;
     k.n_tiles = (uint32_t)tiles;
-    k.F = p->F;
-    k.T = p->T;
-    k.qF = p->F / p->T;
-    k.rF = p->F % p->T;
-    k.Tf = (float)p->T;
-    k.rcpT = rh::lerp_rcp(p->T);  // 0: this T did not pass the exhaustive check of the short division (rh_common.h)
-    k.epoch = p->epoch;
-    k.J = (uint32_t)J;
+    k.J = (uint32_t)g.J;
     k.direct = direct ? 1u : 0u;
-    k.shard_base = p->shard_base;
+    k.shard_base = p->tk.shard_base;
     k.eq_frames = (uint32_t)avail;
-    k.st_mode = sa.mode;
-    k.st_active = (uint32_t)out;
-    k.st_m0 = sa.m0;
-    k.st_g0 = sa.g0;
-    k.st_mfirst = p->st_mfirst;
-    k.st_win = sa.win;
-    k.st_wout = sa.wout;
     k.u = s.uni;
     SblkArgs q;
-    {
-        const uint64_t mb = sa.m0 - std::min<uint64_t>(2, sa.m0 - p->st_mfirst);  // (fewer than two frames in front of the stream's first)
-        const unsigned __int128 pp = (unsigned __int128)mb * F;
-        const uint64_t ib_g = (uint64_t)(pp / T);
-        if (ib_g < sa.g0) return RH_OK;  // (the rows start behind the first tap of frame m0 - 2: not a block of this stream's own making)
-        q.ib = (uint32_t)(ib_g - sa.g0);
-        q.rb = (uint32_t)(pp % T);
-        q.mb_off = (uint32_t)(sa.m0 - mb);
-    }
+    q.ib = g.ib;
+    q.rb = g.rb;
+    q.mb_off = g.mb_off;
     q.uni = s.d_uni;
     q.powD = s.d_pow;
     q.gran = s.d_gran + (size_t)set * s.cap_tiles * 4;
     q.src_off = sa.src_off;
     q.Dmax = s.Dmax;
-    q.P = (uint32_t)P;
+    q.P = (uint32_t)g.P;
     const bool hands = ovl && sa.mode == 1 && sa.wout != nullptr && direct;
     q.hand_in = chained ? s.d_hand + (size_t)s.last_set * 4 : nullptr;
     q.hand_tag = s.last_tag;
     q.hand_out = hands ? s.d_hand + (size_t)set * 4 : nullptr;
     void *args[] = {&k, &q};
-    const uint32_t grid = direct ? (uint32_t)tiles : (((uint32_t)tiles + 7u) & ~7u);
+    const uint32_t grid = direct ? (uint32_t)tiles : rh::rlm::sharded_grid((uint32_t)tiles);
     const hipError_t e = chained ? hipExtLaunchKernel(pick->fn, dim3(grid), dim3(64 * (kSblkWaves + 1)), args, 0, hs, nullptr, nullptr, hipExtAnyOrderLaunch)
                                  : hipLaunchKernel(pick->fn, dim3(grid), dim3(64 * (kSblkWaves + 1)), args, 0, hs);
     if (e != hipSuccess) {
@@ -746,7 +705,7 @@ rh_status sblk_try(rh_rlm *p, uint32_t n_sources, uint64_t avail, uint64_t out, 
     s.seen_version = p->srcs_version;
     if (chained) s.n_chained += 1;
     s.prev_sblk = true;
-    if (!direct) p->shard_base += grid / 8u;
+    rh::rlm::booked(&p->tk, direct, rh::rlm::kShards, grid);
     p->n_tiles = (uint32_t)tiles;
     *taken = true;
     return mark_launch(p, hs);

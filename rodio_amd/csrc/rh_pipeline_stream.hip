@@ -166,7 +166,10 @@ static rh_status stream_block_summed(rh_rlm *p, const float *const *srcs_host, u
                 if (!(gone && (*gone)[s])) live.push_back(s);
             const uint32_t nl = (uint32_t)live.size();
             if (nl == 0) return RH_ERR_INVALID;
-            const bool sum_first = mix_first_applies(p, p->fast, nl, false, false);
+            rh::rlm::RouteIn ri = route_in(p, p->fast);  // (the fast plan: activated below unless the block is k_rlm_sblk's)
+            ri.count = ri.n_sources = nl;
+            ri.st_mode = flush ? 2u : 1u;
+            const bool sum_first = rh::rlm::route(ri) == rh::rlm::kMixed;
             uint64_t src_off = 0;
             bool reuse = sum_first && p->st_tab_version == p->srcs_version && p->st_tab_ptrs.size() == nl && !rh::knob(rh::K_STREAM_UPLOAD_ALWAYS);
             auto row_of = [&](uint32_t k) { return srcs_host[live[k]]; };
