@@ -231,7 +231,10 @@ rh_status rh_echo_mix(float *dst, const float *src, size_t n, size_t delay_sampl
  * Replaces source/mod.rs:628-634 + channel_volume.rs:71-88 in one pass over the input.  x_s = src +
  * s*src_stride holds n interleaved STEREO samples; row s of dst (dst + s*dst_stride) receives
  * 2*floor((n + delay_samples)/2) samples.  gains_dev: DEVICE array [n_streams][2] (rh_spatial_gains
- * per stream).  Bit-exact with the two-step reference chain. */
+ * per stream).  Bit-exact with the two-step reference chain.
+ * RH_ERR_INVALID, nothing written: an odd n (the rows are whole stereo frames), dst or src off an 8-byte boundary, an odd dst_stride with
+ * more than one stream (every row's output frames are stored as 8-byte pairs).  Rows on 16-byte boundaries with n, delay_samples and both
+ * strides multiples of 4 take 16-byte loads and stores; any other shape the 8-byte form -- the same bits. */
 rh_status rh_reverb_spatial(float *dst, const float *src, size_t n, size_t delay_samples, float gain,
                             const float *gains_dev, uint32_t n_streams, size_t src_stride,
                             size_t dst_stride, rh_stream stream);
@@ -551,7 +554,8 @@ rh_status rh_rlm_set_exclusive(rh_rlm *p, int32_t exclusive);
 rh_status rh_rlm_set_mix_first(rh_rlm *p, int32_t enable);
 rh_status rh_rlm_run(rh_rlm *p, float *dst, uint64_t out_capacity_frames, uint64_t *out_frames,
                      rh_stream stream);
-/* The same over the sources [first, first+count) only (a sub-mix; count = 1: one filtered stream). */
+/* The same over the sources [first, first+count) only (a sub-mix; count = 1: one filtered stream).  *out_frames, and the capacity dst
+ * needs, stay those of the whole batch: the frames behind the subset's last source are silence (zeros). */
 rh_status rh_rlm_run_subset(rh_rlm *p, uint32_t first, uint32_t count, float *dst,
                             uint64_t out_capacity_frames, uint64_t *out_frames, rh_stream stream);
 /* Block streaming of the fused path: the same sources arrive block by block (what a `GpuMixer` shim does
@@ -614,7 +618,8 @@ rh_status rh_rlm_stream_overlapped_blocks(rh_rlm *p, uint32_t *blocks);
 /* Diagnostics: blocks of the current stream that ran on the summed state / on one state per source, and recoveries in between. */
 rh_status rh_rlm_stream_stats(rh_rlm *p, uint32_t *summed_blocks, uint32_t *per_source_blocks, uint32_t *recoveries);
 /* No mixer: every source is converted and filtered into its own row, dst + s*dst_stride_frames*channels
- * (equal-length sources only: RH_ERR_UNSUPPORTED otherwise).  One launch for all sources. */
+ * (equal-length STEREO sources only: RH_ERR_UNSUPPORTED otherwise; with more than one source dst_stride_frames is even and at least
+ * *out_frames: RH_ERR_INVALID otherwise -- every row starts on a 16-byte boundary).  One launch for all sources. */
 rh_status rh_rlm_run_batch(rh_rlm *p, float *dst, uint64_t dst_stride_frames, uint64_t *out_frames,
                            rh_stream stream);
 /* Optional: time the candidate launch geometries of the equal-length kernel on the sources that are set

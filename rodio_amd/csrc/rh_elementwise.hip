@@ -613,6 +613,7 @@ rh_status rh_reverb_spatial(float *dst, const float *src, size_t n, size_t delay
     if (frames_out == 0) return RH_OK;
     if (!dst || !src || !gains_dev) return RH_ERR_INVALID;
     if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 7u) return RH_ERR_INVALID;
+    if (n_streams > 1 && dst_stride % 2 != 0) return RH_ERR_INVALID;  // every row's frames are stored as 8-byte pairs
     const bool vec4 = n % 4 == 0 && delay_samples % 4 == 0 && src_stride % 4 == 0 && dst_stride % 4 == 0 &&
                       ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
     // 8 workgroups per CU, split evenly over the 8 XCDs; small jobs get fewer (still a multiple of 8)

@@ -143,9 +143,9 @@ __global__ __launch_bounds__(64, (R <= 4 ? (KV <= 5 ? 5 : 4) : R <= 6 ? 3 : R <=
     }
     int offA[R + 2];
     float wgt[R + 2];
+    const uint32_t dthr = Ns - 1 - i_base;
+    const int thr = (int)((dthr < (1u << 27) ? dthr : (1u << 27)) * FB);  // LDS offset of the sources' last frame
     {
-        const uint32_t dthr = Ns - 1 - i_base;
-        const int thr = (int)((dthr < (1u << 27) ? dthr : (1u << 27)) * FB);
         Cursor c = cursor_at(first ? mfirst : mg0 + m0 - 2, p);
 #pragma unroll
         for (int rr = 0; rr < R + 2; ++rr) {
@@ -206,7 +206,9 @@ __global__ __launch_bounds__(64, (R <= 4 ? (KV <= 5 ? 5 : 4) : R <= 6 ? 3 : R <=
     };
     auto compute = [&](const V (&ta)[R + 2], const V (&tb2)[R + 2], const float g) {
         auto tap = [&](int rr) -> V {
-            const V a = ta[rr], b = tb2[rr];
+            // the sources' last frame is emitted verbatim: its second tap lies behind the row (the rest of the row's last 16-byte vector, or
+            // the re-fetched vector) and must not reach the arithmetic -- b = a gives a + (a - a) * 0 / T = a whatever lies there
+            const V a = ta[rr], b = (edge && offA[rr] == thr) ? a : tb2[rr];
             V x;
 #pragma unroll
             for (int c = 0; c < C; ++c) {

@@ -1,0 +1,196 @@
+"""Guard zones and poisoned surroundings for the kernels' rows (a plain helper module like fallback_cases.py: no fixtures).
+
+A kernel's `dst`, `state` and `scratch` live in SENTINEL arenas: one device buffer whose every 32-bit word holds a quiet NaN with a payload
+(0x7fc5a5a5) before the call, the row(s) `lead` elements behind a 16-byte boundary, at least GUARD words in front and behind, and sentinel
+in the gaps between batched rows.  Its sources live in POISON arenas: the samples between two zones of another quiet NaN (0x7fc00bad), so a
+read outside a row that reaches the arithmetic comes out as NaN instead of as `junk * 0`.  `check` works on the uint32 words that were copied
+back: every guard and gap word must still be the sentinel (nothing stored outside a row) and every row word must differ from it (nothing
+left unwritten), except behind the count an entry reports (`*out_n` of rh_chirp, the samples a take admits), where it must still be there.
+
+The layouts and `check` are pure numpy (tests/test_arena_cpu.py holds them on arrays spoiled by hand); only `Arena` touches torch."""
+import numpy as np
+
+GUARD = 1024  # words in front of the first row and behind the last one: a multiple of 4, wider than any vector or tile tail
+SENTINEL = 0x7FC5A5A5  # quiet NaN, payload 0x5a5a5: what an output arena holds before the call
+POISON = 0x7FC00BAD  # quiet NaN, another payload: what surrounds a source
+INT_SENTINEL = 0x80000001  # for integer rows: a value the tests' data cannot produce (function codes, small counters)
+
+
+class Layout:
+    """Where the rows lie in a buffer of `total` 32-bit words: row r covers words [starts[r], starts[r] + n); everything else is guard or gap
+    and holds `fill`."""
+
+    def __init__(self, total, starts, n, fill):
+        self.total, self.starts, self.n, self.fill = int(total), [int(s) for s in starts], int(n), int(fill)
+
+    @property
+    def rows(self):
+        return len(self.starts)
+
+
+def layout_rows(S, n, stride, lead=0, fill=SENTINEL):
+    """S rows of n words, `stride` words apart (stride >= n), the first one `lead` words behind a 16-byte boundary."""
+    assert S >= 1 and n >= 0 and stride >= n and 0 <= lead < 4 and GUARD % 4 == 0
+    span = (S - 1) * stride + n
+    return Layout(GUARD + lead + span + GUARD, [GUARD + lead + r * stride for r in range(S)], n, fill)
+
+
+def layout(n, lead=0, fill=SENTINEL):
+    return layout_rows(1, n, n, lead, fill)
+
+
+def build(lay, rows=None):
+    """The uint32 words of a fresh arena: `fill` everywhere, row r = the 32-bit words of rows[r] where rows are given."""
+    w = np.full(lay.total, lay.fill, dtype=np.uint32)
+    if rows is not None:
+        assert len(rows) == lay.rows
+        for s, x in zip(lay.starts, rows):
+            x = np.ascontiguousarray(x).reshape(-1)
+            assert x.dtype.itemsize == 4 and x.size == lay.n
+            w[s: s + lay.n] = x.view(np.uint32)
+    return w
+
+
+def _where(lay, i):
+    """Word i of the buffer as an offset relative to a row: the row it lies in or behind, row 0 for the leading guard."""
+    r = max([k for k, s in enumerate(lay.starts) if s <= i], default=0)
+    return f"offset {i - lay.starts[r]:+d} relative to row {r} (rows of {lay.n} words)"
+
+
+def check(host_words, lay, written=None):
+    """host_words: the arena's words after the call (uint32).  written: words the entry's contract says it writes, one count for every row or
+    a count per row; None = all n.  Raises AssertionError that names the first offending offset; returns the rows' words, shape (n,) for
+    one row and (rows, n) otherwise (a copy)."""
+    w = np.asarray(host_words)
+    assert w.dtype == np.uint32 and w.ndim == 1 and w.size == lay.total, "check() wants the arena's uint32 words"
+    counts = [lay.n] * lay.rows if written is None else ([int(written)] * lay.rows if np.isscalar(written) else [int(c) for c in written])
+    assert len(counts) == lay.rows and all(0 <= c <= lay.n for c in counts)
+    must_write = np.zeros(lay.total, dtype=bool)
+    for s, c in zip(lay.starts, counts):
+        must_write[s: s + c] = True
+    stored = np.flatnonzero(~must_write & (w != np.uint32(lay.fill)))
+    if stored.size:
+        i = int(stored[0])
+        raise AssertionError(f"stored outside what the entry may write: {stored.size} word(s), the first at {_where(lay, i)}: 0x{int(w[i]):08x}")
+    missed = np.flatnonzero(must_write & (w == np.uint32(lay.fill)))
+    if missed.size:
+        i = int(missed[0])
+        raise AssertionError(f"never written: {missed.size} word(s) still hold the sentinel, the first at {_where(lay, i)}")
+    out = np.stack([w[s: s + lay.n] for s in lay.starts]).copy()
+    return out[0] if lay.rows == 1 else out
+
+
+def check_guards(host_words, lay):
+    """Only the words outside the rows (a scratch buffer: the entry may use as much of it as it likes, and nothing beside it)."""
+    w = np.asarray(host_words)
+    assert w.dtype == np.uint32 and w.ndim == 1 and w.size == lay.total, "check_guards() wants the arena's uint32 words"
+    inside = np.zeros(lay.total, dtype=bool)
+    for s in lay.starts:
+        inside[s: s + lay.n] = True
+    stored = np.flatnonzero(~inside & (w != np.uint32(lay.fill)))
+    if stored.size:
+        i = int(stored[0])
+        raise AssertionError(f"stored outside what the entry may write: {stored.size} word(s), the first at {_where(lay, i)}: 0x{int(w[i]):08x}")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same(a, b):
+    """Two blocks of floats hold the same bits (compared as uint32: a NaN equals itself only bit for bit); shapes are flattened."""
+    a, b = np.asarray(a, np.float32).reshape(-1), np.asarray(b, np.float32).reshape(-1)
+    return a.shape == b.shape and bool(np.array_equal(bits(a), bits(b)))
+
+
+class Arena:
+    """A layout on the device.  ptr(r) is the address of row r; words() copies the buffer back; check() is check() on that copy;
+    unchanged() holds the buffer against what was uploaded (sources, function tables: nothing may write them)."""
+
+    def __init__(self, lay, rows=None):
+        import torch
+
+        self.layout = lay
+        self.initial = build(lay, rows)
+        self.buf = torch.from_numpy(self.initial.view(np.int32).copy()).cuda()
+        assert self.buf.data_ptr() % 16 == 0
+
+    def ptr(self, r=0):
+        return self.buf.data_ptr() + 4 * self.layout.starts[r]
+
+    def words(self):
+        import torch
+
+        torch.cuda.synchronize()
+        return self.buf.cpu().numpy().view(np.uint32)
+
+    def check(self, written=None, dtype=np.float32):
+        return check(self.words(), self.layout, written).view(dtype)
+
+    def check_guards(self):
+        check_guards(self.words(), self.layout)
+
+    def unchanged(self):
+        w = self.words()
+        bad = np.flatnonzero(w != self.initial)
+        assert bad.size == 0, f"a read-only arena was written: {bad.size} word(s), the first at {_where(self.layout, int(bad[0]))}"
+
+
+def dst_arena(n, lead=0, dtype=np.float32):
+    """n elements of a 32-bit type between sentinel guards, the row `lead` elements behind a 16-byte boundary."""
+    return Arena(layout(n, lead, SENTINEL if np.dtype(dtype).kind == "f" else INT_SENTINEL))
+
+
+def dst_arena_rows(S, n, stride, lead=0):
+    return Arena(layout_rows(S, n, stride, lead, SENTINEL))
+
+
+def src_arena(x, lead=0):
+    """x (a 32-bit type) between two poison zones."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    return Arena(layout(x.size, lead, POISON), [x])
+
+
+def src_arena_rows(xs, stride, lead=0):
+    xs = [np.ascontiguousarray(x).reshape(-1) for x in xs]
+    return Arena(layout_rows(len(xs), xs[0].size, stride, lead, POISON), xs)
+
+
+def inplace_arena(x, lead=0):
+    """dst == src: the signal between SENTINEL guards (a signal does not hold the sentinel's payload, so check() still sees the guards)."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    return Arena(layout(x.size, lead, SENTINEL), [x])
+
+
+def inplace_arena_rows(xs, stride, lead=0):
+    xs = [np.ascontiguousarray(x).reshape(-1) for x in xs]
+    return Arena(layout_rows(len(xs), xs[0].size, stride, lead, SENTINEL), xs)
+
+
+def state_arena(k, init=None):
+    """Exactly k 32-bit words of the caller's initial values (zeros by default) between sentinel guards, on a 16-byte boundary: the end is
+    usually inside a vector."""
+    v = np.zeros(k, np.float32) if init is None else np.ascontiguousarray(init).reshape(-1)
+    assert v.size == k
+    return Arena(layout(k, 0, SENTINEL), [v])
+
+
+def plain(x, rows=1, stride=None):
+    """The same rows in friendly surroundings, for the bit comparisons of arena against plain runs: zeros around and between the sources."""
+    import torch
+
+    xs = np.ascontiguousarray(x).reshape(rows, -1)
+    stride = stride or xs.shape[1]
+    buf = np.zeros(GUARD + rows * stride + GUARD, dtype=xs.dtype)
+    for r in range(rows):
+        buf[GUARD + r * stride: GUARD + r * stride + xs.shape[1]] = xs[r]
+    t = torch.from_numpy(buf).cuda()
+    return t, t.data_ptr() + GUARD * xs.dtype.itemsize
+
+
+def plain_dst(n_words):
+    """A fresh zeroed dst for the plain run."""
+    import torch
+
+    t = torch.zeros(n_words + 8, dtype=torch.float32, device="cuda")
+    return t, t.data_ptr()
