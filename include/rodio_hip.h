@@ -218,6 +218,34 @@ rh_status rh_channel_volume_steps(float *dst, const float *src, size_t frames, u
                                   uint64_t first, uint64_t gain_period, const float *gains_dev, uint32_t n_gains,
                                   uint64_t factor_first, uint64_t factor_period, const float *factors_dev,
                                   uint32_t n_factors, rh_stream stream);
+/* BltFilter whose formula a periodic_access closure changes (blt.rs:68-91, 234-252): coefficients by STEPS, memory kept.
+ * Sample i of a stream's block (interleaved, i < frames*channels) is filtered with entry
+ * (first + i) / period - first / period of that stream's table; an entry is {b0,b1,b2,a1,a2} as rh_biquad_coeffs gives them.
+ * first and period count SAMPLES of the stream, as in rh_amplify_steps: a change reaches channel c with the first sample of that
+ * channel at or after the boundary, so it may fall in mid-frame.
+ * coeffs_dev: device memory, n_steps entries per stream, table_stride floats between two streams' tables (0: all streams share one).
+ * state, n_streams, layout of the batch: as rh_biquad ({x1,x2,y1,y2} per channel; NULL: a zero state that is not kept).  A stream may
+ * change between rh_biquad, mode 0 and mode 1 from block to block.  Rows start at any 4-byte address.  frames == 0: nothing happens,
+ * state included.  RH_ERR_INVALID: period == 0, channels == 0, fewer entries than the block reaches, 0 < table_stride < 5 * n_steps.
+ * No host synchronisation, no allocation per call.
+ * mode 0: rodio's operation order (blt.rs:559, left to right, unfused), bit for bit -- rh_biquad mode 0 with each step's entry.  The
+ *   drop-in, and the default of the host mirror's live_low_pass / live_high_pass.
+ * mode 1: time-parallel.  One workgroup per stream walks the stream's tiles and carries the state itself (no workgroup waits for
+ *   another); inside a tile the runs of the lanes are joined by a scan of their affine state maps.  THE CONTRACT: the result is the
+ *   f64 evaluation of the same recurrence, every sample rounded to f32 once (within 2^-23 * max(1, peak) of it; the state leaves as
+ *   f32).  That is within 1e-5 of rodio's own f32 recurrence for a full-scale source while the table SWEEPS smoothly through filters
+ *   that pass rh_filter_scan_ok; it is NOT bounded across jumps between distant filters, where the direct-form state of one filter is
+ *   a large transient in the other and rodio's own rounding noise grows with it -- there mode 0 is the drop-in.  f32 recurrence
+ *   against the f64 one, full-scale uniform noise at 48 kHz, the table changing every U samples:
+ *     low_pass 100 <-> 8000 Hz, geometric sweep, up or down          2.8e-6 / 3.5e-6   (output peak 0.8)
+ *     high_pass 600 -> 6000 Hz, geometric sweep                      4.5e-6            (1.45)
+ *     stereo U = 441, 6 channels U = 1323, U = 1, q = 2.0            <= 4.6e-6         (up to 2.1)
+ *     low_pass ALTERNATING 100 / 8000 Hz every step                  3.8e-4            (12.6)
+ *     high_pass alternating 600 / 6000 Hz                            1.25e-5           (4.9)
+ *   1 to 8 channels; more channels, and a dst that overlaps src (dst == src is valid), run in mode 0 -- never an error. */
+rh_status rh_biquad_steps(float *dst, const float *src, uint64_t frames, uint32_t channels, uint32_t n_streams,
+                          uint64_t first, uint64_t period, const float *coeffs_dev, uint32_t n_steps, uint64_t table_stride,
+                          float *state, int32_t mode, rh_stream stream);
 
 /* ---- reverb = Mix(x, Delay(Amplify(x))): src/source/mod.rs:628-634, delay.rs:8-16,68-75,
  * mix.rs:43-53.  delay_samples counts INTERLEAVED samples (delay.rs:14).  dst holds

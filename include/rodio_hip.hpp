@@ -1433,6 +1433,21 @@ public:
         (*v_)[1] = g[1];
     }
 };
+/// BltFilter::to_low_pass / to_high_pass and their _with_q forms (blt.rs:68-91): the formula is replaced, the filter's memory stays
+/// (set_formula, blt.rs:234-252: new coefficients for the sample rate of the filter's input).
+class LiveFilter {
+public:
+    LiveFilter(std::vector<float> *v, std::uint32_t rate) : v_(v), rate_(rate) {}
+    void to_low_pass(std::uint32_t freq) { to_low_pass_with_q(freq, 0.5f); }
+    void to_high_pass(std::uint32_t freq) { to_high_pass_with_q(freq, 0.5f); }
+    void to_low_pass_with_q(std::uint32_t freq, float q) { set(0, freq, q); }
+    void to_high_pass_with_q(std::uint32_t freq, float q) { set(1, freq, q); }
+
+private:
+    void set(int kind, std::uint32_t freq, float q) { check(rh_biquad_coeffs(kind, freq, q, rate_, v_->data()), "rh_biquad_coeffs"); }
+    std::vector<float> *v_;
+    std::uint32_t rate_;
+};
 class Controls;
 namespace detail {
 /// The schedule of a chain's periodic_access() closures and the values they set (GpuSource::periodic_access).  Every adjustable
@@ -1441,13 +1456,14 @@ namespace detail {
 /// the order rodio calls them: by sample, and at one sample the access point further down the chain first (its next() runs its
 /// closure before it asks its input).  What a call sets holds from its access sample on (steps).
 struct LiveController {
-    enum Kind { Amplify = 0, ChannelVolume = 1, Spatial = 2 };
+    enum Kind { Amplify = 0, ChannelVolume = 1, Spatial = 2, Filter = 3 };
     struct Param {
         int kind;
         std::size_t stage;       // the chain's stage that applies it
         std::vector<float> cur;  // what the closures have set last
         std::deque<std::pair<std::uint64_t, std::vector<float>>> steps;  // (first sample, values): the values from that sample on
         std::size_t fused = SIZE_MAX;  // a channel volume: the amplify whose factor its launch applies
+        std::uint32_t rate = 0;        // a filter: the sample rate its coefficients are made for
     };
     struct Access {
         std::size_t stage;  // the access point's stage: it reaches the parameters of the stages in front of it
@@ -1526,21 +1542,27 @@ struct LiveUpload {
 };
 }  // namespace detail
 /// The argument of a periodic_access() closure: the adjustable stages in front of the access point, k-th of each kind in the chain's
-/// order (live_amplify, live_channel_volume, live_spatial), and the index of the access (call k runs before sample k * U).
+/// order (live_amplify, live_channel_volume, live_spatial, live_low_pass / live_high_pass), and the index of the access (call k runs
+/// before sample k * U).
 class Controls {
 public:
     Controls(detail::LiveController *c, std::size_t stage, std::uint64_t index) : c_(c), stage_(stage), index_(index) {}
     LiveAmplify amplify(std::size_t k = 0) { return LiveAmplify(find(detail::LiveController::Amplify, k)); }
     LiveChannelVolume channel_volume(std::size_t k = 0) { return LiveChannelVolume(find(detail::LiveController::ChannelVolume, k)); }
     LiveSpatial spatial(std::size_t k = 0) { return LiveSpatial(find(detail::LiveController::Spatial, k)); }
+    LiveFilter filter(std::size_t k = 0) {
+        detail::LiveController::Param &p = param(detail::LiveController::Filter, k);
+        return LiveFilter(&p.cur, p.rate);
+    }
     std::uint64_t access_index() const { return index_; }
 
 private:
-    std::vector<float> *find(int kind, std::size_t k) {
+    detail::LiveController::Param &param(int kind, std::size_t k) {
         for (detail::LiveController::Param &p : c_->params)
-            if (p.stage < stage_ && p.kind == kind && k-- == 0) return &p.cur;
+            if (p.stage < stage_ && p.kind == kind && k-- == 0) return p;
         throw std::out_of_range("periodic_access: no such adjustable stage in front of the access point");
     }
+    std::vector<float> *find(int kind, std::size_t k) { return &param(kind, k).cur; }
     detail::LiveController *c_;
     std::size_t stage_;
     std::uint64_t index_;
@@ -2240,6 +2262,24 @@ public:
         check(rh_spatial_gains(emitter, left_ear, right_ear, g), "rh_spatial_gains");
         return live_cv({g[0], g[1]}, detail::LiveController::Spatial);
     }
+    /// low_pass / high_pass whose formula a periodic_access() closure behind it replaces (BltFilter::to_low_pass / to_high_pass and their
+    /// _with_q forms, blt.rs:68-91; the filter's memory stays, blt.rs:234-252): Controls::filter(k).  One rh_biquad_steps launch a block; a change
+    /// reaches every channel with its first sample at or after the access, in mid-frame too.  Rodio's operation order, bit for bit
+    /// (without an access point behind it: the bits of exact_filters().low_pass(freq)); live_filters_time_parallel() selects the other
+    /// evaluation.  Like the other adjustable stages it refuses an upstream that changes its format between spans (`.uniform()` in front),
+    /// and its size_hint / total_duration are its input's (blt.rs:144-174).
+    GpuSource &live_low_pass(std::uint32_t freq) { return live_blt(0, freq, 0.5f); }
+    GpuSource &live_high_pass(std::uint32_t freq) { return live_blt(1, freq, 0.5f); }
+    GpuSource &live_low_pass_with_q(std::uint32_t freq, float q) { return live_blt(0, freq, q); }
+    GpuSource &live_high_pass_with_q(std::uint32_t freq, float q) { return live_blt(1, freq, q); }
+    /// The chain's live filters evaluate time-parallel (rh_biquad_steps mode 1) -- off by default.  THE CONTRACT (rodio_hip.h): the f64
+    /// evaluation of the same recurrence, every sample rounded to f32 once; within 1e-5 of rodio's own f32 recurrence for a full-scale
+    /// source while the closures SWEEP smoothly through filters that pass rh_filter_scan_ok, and not bounded across jumps between distant
+    /// filters (100 Hz <-> 8 kHz from one access to the next: rodio's own rounding noise reaches 4e-4 there) -- the default is the drop-in.
+    GpuSource &live_filters_time_parallel(bool on = true) {
+        live_time_parallel_ = on;
+        return *this;
+    }
     /// `periodic_access(period, f)` (periodic.rs:9-24,63-77): f runs before sample 0, U, 2U, ... of the stream here, U =
     /// rh_periodic_update_samples(period, rate, channels) of the format here, and reaches the adjustable stages in front through its
     /// Controls.  Refused (RH_ERR_UNSUPPORTED) when a stage between an adjustable stage and this point does not hand on one sample per
@@ -2792,6 +2832,42 @@ private:
     }
     // the first sample any stage may compute again (a seek goes back to the consumer's frame): steps in front of it can go
     std::uint64_t live_floor(std::uint64_t pos) const { return live_seekable() ? std::min<std::uint64_t>(pos, handed_out() - handed_out() % ch_) : pos; }
+    GpuSource &live_blt(int kind, std::uint32_t freq, float q) {  // live_low_pass / live_high_pass (+ _with_q)
+        const std::uint16_t ch = ch_;
+        detail::LiveController &lc = live_controller(kind ? "live_high_pass" : "live_low_pass");
+        const std::size_t self = stages_.size();
+        std::vector<float> co(5);
+        check(rh_biquad_coeffs(kind, freq, q, rate_, co.data()), "rh_biquad_coeffs");
+        lc.params.push_back(detail::LiveController::Param{detail::LiveController::Filter, self, co, {{0, co}}, SIZE_MAX, rate_});
+        const std::size_t me = lc.params.size() - 1;
+        auto pos = std::make_shared<std::uint64_t>(0);
+        auto st = state(4u * ch);
+        auto fc = std::make_shared<FrameCarry>();
+        auto up = std::make_shared<detail::LiveUpload>();
+        std::shared_ptr<detail::LiveController> live = live_;
+        push([this, live, me, pos, st, fc, up, ch](Ctx &c) {
+            if (c.n) live->ensure(*pos + c.n, false);
+            // run_framewise works on the kept samples of an open frame and then the block's: its first call takes the whole frames, from the
+            // stream's sample `base`; a second one takes the open frame behind them, completed by zeros
+            const std::uint64_t base = *pos - fc->n;
+            const std::size_t whole = (fc->n + c.n) / ch;
+            bool head = whole != 0;
+            const std::size_t r = run_framewise(c, ch, *fc, st->get(), 4u * ch, [&](float *out, const float *in, std::size_t frames, float *state) {
+                const std::uint64_t at = head ? base : base + (std::uint64_t)whole * ch;
+                head = false;
+                detail::LiveController::Param &p = live->params[me];
+                const std::uint64_t n = (std::uint64_t)frames * ch, per = live->period(p), k = detail::LiveController::steps_needed(at, per, n);
+                live->table(p, live_floor(at), at, per, n, up->staging(5 * k));
+                check(rh_biquad_steps(out, in, frames, ch, 1, at, per, up->upload(5 * k, c.stream), (std::uint32_t)k, 0, state, live_time_parallel_ ? 1 : 0, c.stream), "rh_biquad_steps");
+            });
+            *pos += c.n;
+            return r;
+        }).on_seek([st, ch, fc, sm = stream_](Nanos) {  // blt.rs:350-377
+            check(rh_memset(st->get(), 0, 4u * ch * sizeof(float), sm), "rh_memset");
+            fc->n = fc->lead = 0;
+        });
+        return live_stage_done(pos);
+    }
     GpuSource &live_cv(std::vector<float> gains, int kind) {  // live_channel_volume / live_spatial
         const std::uint16_t in_ch = ch_;
         const std::uint16_t out_ch = (std::uint16_t)gains.size();
@@ -2851,6 +2927,7 @@ private:
     }
 
     std::shared_ptr<detail::LiveController> live_;  // adjustable stages / periodic_access (null: none)
+    bool live_time_parallel_ = false;               // live filters: rh_biquad_steps mode 1
     BoxSource up_;
     std::size_t block_frames_;
     std::uint16_t ch_ = 0;

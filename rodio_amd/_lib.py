@@ -125,6 +125,7 @@ SIGNATURES = {
     "rh_periodic_update_samples": (u64, [u64, u32, u32]),
     "rh_amplify_steps": (i32, [vp, vp, sz, u64, u64, vp, u32, vp]),
     "rh_channel_volume_steps": (i32, [vp, vp, sz, u32, u32, u64, u64, vp, u32, u64, u64, vp, u32, vp]),
+    "rh_biquad_steps": (i32, [vp, vp, u64, u32, u32, u64, u64, vp, u32, u64, vp, i32, vp]),
     "rh_delay_samples": (u64, [u64, u32, u32]),
     "rh_echo_mix": (i32, [vp, vp, sz, sz, f32, vp]),
     "rh_resample_out_frames": (i32, [u64, u32, u32, u32, u64, C.POINTER(u64)]),

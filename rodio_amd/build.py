@@ -77,6 +77,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 DRIVERS = {
     "host_mirror_test": dict(lib=True, fake=True),
     "live_test": dict(lib=True, fake=True, fakes=["fake_live.cpp"]),
+    "live_filter_test": dict(lib=True, fake=True, fakes=["fake_live.cpp", "fake_live_filter.cpp"]),  # live_low_pass / live_high_pass under periodic_access
     "generators_test": dict(hdrs=["rh_generators.h"], fpc=True),  # the phase walk against brute-force stepping, and the serial f32 phases
     "generators_mirror_test": dict(lib=True, fake=True, hdrs=["rh_generators.h"], fakes=["fake_generators.cpp"]),
     "noise_mirror_test": dict(lib=True, fake=True, fpc=True, hdrs=["rh_noise.h"], fakes=["fake_noise.cpp"]),

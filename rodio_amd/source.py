@@ -995,6 +995,35 @@ def channel_volume_steps(x, in_ch: int, out_ch: int, first: int, gain_period: in
     return out
 
 
+# rh_biquad_steps mode 1 (k_biquad_steps_scan in csrc/rh_live.hip): frames a lane owns in a tile (kRun) and frames a tile
+# (kScanBlock * kRun).  tests/test_live_filter_cpu.py holds the two against the kernel's source.
+BIQUAD_STEPS_RUN = 8
+BIQUAD_STEPS_TILE = 256 * BIQUAD_STEPS_RUN
+
+
+def biquad_steps(x, channels: int, first: int, period: int, coeffs, n_streams: int = 1, state=None, mode: int = 0, out=None):
+    """rh_biquad_steps over the device tensor x (n_streams rows of whole interleaved frames, back to back): sample i of a row is
+    filtered with coeffs[(first + i) // period - first // period] ({b0,b1,b2,a1,a2} per entry).  coeffs: [steps, 5] shared by the
+    rows, or [n_streams, steps, 5].  state: a float32 device tensor of n_streams * channels * 4 ({x1,x2,y1,y2} per channel),
+    updated in place, or None.  mode 0: rodio's bits; mode 1: the f64 evaluation, time-parallel (rodio_hip.h).  `out` may be x."""
+    _ensure()
+    torch = _t()
+    co = coeffs if isinstance(coeffs, torch.Tensor) else np.ascontiguousarray(coeffs, dtype=np.float32)
+    if co.ndim == 3:
+        assert co.shape[0] == n_streams and co.shape[2] == 5
+        n_steps, stride = co.shape[1], co.shape[1] * 5
+    else:
+        assert co.ndim == 2 and co.shape[1] == 5
+        n_steps, stride = co.shape[0], 0
+    t = _table(co)
+    frames = x.numel() // (channels * n_streams) if channels and n_streams else 0
+    if out is None:
+        out = _dev_empty(x.numel())
+    check(lib.rh_biquad_steps(_ptr(out), _ptr(x), frames, int(channels), int(n_streams), int(first), int(period), _ptr(t), n_steps, stride,
+                              _ptr(state) if state is not None else None, int(mode), _stream()), "rh_biquad_steps")
+    return out
+
+
 # ---- sources that start on the device: rodio's synthetic generators (rh_signal_generate / rh_chirp) -------------------------
 GEN_FUNCTIONS = {"sine": 0, "triangle": 1, "square": 2, "sawtooth": 3}  # rodio's Function (signal_generator.rs:24-30), RH_GEN_*
 DEFAULT_SAMPLE_RATE = 48000  # rodio::DEFAULT_SAMPLE_RATE

@@ -617,7 +617,7 @@ impl HintState {
 }
 
 // ------------------------------------------------------------------------------------------------ parameters that change while a source plays ----
-struct LiveParam { kind: u8, stage: usize, cur: Vec<f32>, steps: Vec<(u64, Vec<f32>)> }   // kind: 0 amplify, 1 channel volume, 2 spatial; steps: (first sample, values)
+struct LiveParam { kind: u8, stage: usize, cur: Vec<f32>, steps: Vec<(u64, Vec<f32>)>, rate: u32 }   // kind: 0 amplify, 1 channel volume, 2 spatial, 3 filter ({b0,b1,b2,a1,a2}; rate: what its coefficients are made for); steps: (first sample, values)
 struct LiveAccess { stage: usize, u: u64, f: Box<dyn FnMut(&mut Controls) + Send>, next: u64 }
 struct LiveState {
     params: Vec<LiveParam>, accesses: Vec<LiveAccess>, calls: u64,
@@ -639,6 +639,16 @@ impl Controls<'_> {
         let mut g = [0f32; 2];
         ck(unsafe { rh_spatial_gains(emitter.as_ptr(), left_ear.as_ptr(), right_ear.as_ptr(), g.as_mut_ptr()) }, "rh_spatial_gains");
         self.find(2, k).copy_from_slice(&g);
+    }
+    // BltFilter::to_low_pass / to_high_pass (+ _with_q), blt.rs:68-91: the formula is replaced, the filter's memory stays (blt.rs:234-252)
+    pub fn to_low_pass(&mut self, k: usize, freq: u32) { self.set_formula(k, 0, freq, 0.5); }
+    pub fn to_high_pass(&mut self, k: usize, freq: u32) { self.set_formula(k, 1, freq, 0.5); }
+    pub fn to_low_pass_with_q(&mut self, k: usize, freq: u32, q: f32) { self.set_formula(k, 0, freq, q); }
+    pub fn to_high_pass_with_q(&mut self, k: usize, freq: u32, q: f32) { self.set_formula(k, 1, freq, q); }
+    fn set_formula(&mut self, k: usize, kind: i32, freq: u32, q: f32) {
+        let stage = self.stage;
+        let p = self.params.iter_mut().filter(|p| p.stage < stage && p.kind == 3).nth(k).expect("periodic_access: no such live filter in front of the access point");
+        ck(unsafe { rh_biquad_coeffs(kind, freq, q, p.rate, p.cur.as_mut_ptr()) }, "rh_biquad_coeffs");
     }
 }
 impl Default for LiveState { fn default() -> Self { LiveState { params: Vec::new(), accesses: Vec::new(), calls: 0, positions: Vec::new(), floor: u64::MAX } } }
@@ -710,6 +720,7 @@ pub struct GpuSource<I: Source> {
     pulled_total: u64,             // samples pulled from the upstream, whatever was sought in between
     last_kind: u8,                 // the adapter pushed last: 1 a `uniform`, 2 a filter right behind a `uniform`, 0 anything else
     live: Option<Arc<Mutex<LiveState>>>,   // adjustable stages / periodic_access (None: none)
+    live_time_parallel: Arc<std::sync::atomic::AtomicBool>,   // live filters: rh_biquad_steps mode 1
 }
 type Arc<T> = std::sync::Arc<T>;
 type Mutex<T> = std::sync::Mutex<T>;
@@ -720,7 +731,8 @@ impl<I: Source> GpuSource<I> {
         let (ch, rate) = (upstream.channels().get(), upstream.sample_rate().get());
         GpuSource { up: upstream, block_frames: block_frames.max(1), ch, rate, in_ch: ch, in_rate: rate, stages: Vec::new(), reader: SpanReader::new(),
                     pieces: Vec::new(), span_aware: false, scan_kernels: false, may_cut: false, filter_mode: 0, a: DeviceBuf::new(), b: DeviceBuf::new(), pump: Pump::new(),
-                    hint: Arc::new(Mutex::new(HintState::default())), durs: Vec::new(), pulled_total: 0, last_kind: 0, live: None }
+                    hint: Arc::new(Mutex::new(HintState::default())), durs: Vec::new(), pulled_total: 0, last_kind: 0, live: None,
+                    live_time_parallel: Arc::new(std::sync::atomic::AtomicBool::new(false)) }
     }
     /// `total_duration()` as rodio's adapters answer it, adapter by adapter: the input's behind the ones that keep it (amplify.rs:95-97,
     /// blt.rs:171-173, limit.rs:592-594, agc.rs:588-590, channel_volume.rs:119-121), plus the delay behind `delay` (delay.rs:111-115), the
@@ -1063,7 +1075,7 @@ impl<I: Source> GpuSource<I> {
     /// Amplify whose factor a periodic_access() closure behind it sets (amplify.rs:27-35,64).
     pub fn live_amplify(mut self, factor: f32) -> Self {
         let live = self.live_state();
-        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind: 0, stage: self.stages.len(), cur: vec![factor], steps: vec![(0, vec![factor])] }); (l.params.len() - 1, l.position()) };
+        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind: 0, stage: self.stages.len(), cur: vec![factor], steps: vec![(0, vec![factor])], rate: 0 }); (l.params.len() - 1, l.position()) };
         self.push(move |c| {
             let pos = at.load(std::sync::atomic::Ordering::Relaxed);
             let (per, tab) = live.lock().unwrap().schedule(me, pos, c.n as u64);
@@ -1075,6 +1087,43 @@ impl<I: Source> GpuSource<I> {
             at.store(pos + c.n as u64, std::sync::atomic::Ordering::Relaxed);
             c.n
         }, |n, _| n, 0);
+        self
+    }
+    /// low_pass / high_pass whose formula a periodic_access() closure behind it replaces (Controls::to_low_pass / to_high_pass and their
+    /// _with_q forms: blt.rs:68-91; the filter's memory stays, blt.rs:234-252).  One rh_biquad_steps launch a block, rodio's operation order
+    /// bit for bit; a change reaches every channel with its first sample at or after the access.  (As `low_pass` here: whole frames a block.)
+    pub fn live_low_pass(self, freq: u32) -> Self { self.live_blt(0, freq, 0.5) }
+    pub fn live_high_pass(self, freq: u32) -> Self { self.live_blt(1, freq, 0.5) }
+    pub fn live_low_pass_with_q(self, freq: u32, q: f32) -> Self { self.live_blt(0, freq, q) }
+    pub fn live_high_pass_with_q(self, freq: u32, q: f32) -> Self { self.live_blt(1, freq, q) }
+    /// The chain's live filters evaluate time-parallel (rh_biquad_steps mode 1); off by default.  THE CONTRACT (rodio_hip.h): the f64
+    /// evaluation of the same recurrence, every sample rounded to f32 once -- within 1e-5 of rodio's own f32 recurrence for a full-scale
+    /// source while the closures sweep smoothly through filters that pass rh_filter_scan_ok, not bounded across jumps between distant
+    /// filters, where the default is the drop-in.
+    pub fn live_filters_time_parallel(self, on: bool) -> Self { self.live_time_parallel.store(on, std::sync::atomic::Ordering::Relaxed); self }
+    fn live_blt(mut self, kind: i32, freq: u32, q: f32) -> Self {
+        let (ch, rate) = (self.ch as u32, self.rate);
+        let mut co = vec![0f32; 5];
+        ck(unsafe { rh_biquad_coeffs(kind, freq, q, rate, co.as_mut_ptr()) }, "rh_biquad_coeffs");
+        let live = self.live_state();
+        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind: 3, stage: self.stages.len(), cur: co.clone(), steps: vec![(0, co)], rate }); (l.params.len() - 1, l.position()) };
+        let st = self.state(4 * ch as usize);
+        let (st2, sm, tp) = (st.clone(), self.pump.stream as usize, self.live_time_parallel.clone());
+        let stage = self.push(move |c| {
+            let pos = at.load(std::sync::atomic::Ordering::Relaxed);
+            let frames = c.n / ch as usize;
+            let n = frames as u64 * ch as u64;
+            let (per, tab) = live.lock().unwrap().schedule(me, pos, n);
+            let mut d = DeviceBuf::new();
+            d.reserve(tab.len().max(1));
+            ck(unsafe { rh_memcpy_h2d(d.p.cast(), tab.as_ptr().cast(), tab.len() * 4, c.stream) }, "rh_memcpy_h2d");
+            let mode = if tp.load(std::sync::atomic::Ordering::Relaxed) { 1 } else { 0 };
+            ck(unsafe { rh_biquad_steps(c.out, c.inp, frames as u64, ch, 1, pos, per, d.p, (tab.len() / 5) as u32, 0, st.0.p, mode, c.stream) }, "rh_biquad_steps");
+            ck(unsafe { rh_stream_synchronize(c.stream) }, "rh_stream_synchronize");   // (d goes when the block's launch has run)
+            at.store(pos + n, std::sync::atomic::Ordering::Relaxed);
+            n as usize
+        }, |n, _| n, 0);
+        stage.on_seek = Some(Box::new(move |_| ck(unsafe { rh_memset(st2.0.p.cast(), 0, 4 * ch as usize * 4, sm as RhStream) }, "rh_memset")));   // blt.rs:350-377
         self
     }
     /// ChannelVolume whose gains a periodic_access() closure behind it sets (channel_volume.rs:41-43,71-88).
@@ -1090,7 +1139,7 @@ impl<I: Source> GpuSource<I> {
         assert!(out_ch > 0 && out_ch <= 16, "live_channel_volume: 1 to 16 output channels");
         assert!(self.live.is_none(), "live_channel_volume / live_spatial: the chain's first adjustable stage (it changes the sample count that the others count)");
         let live = self.live_state();
-        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind, stage: self.stages.len(), cur: gains.clone(), steps: vec![(0, gains)] }); (l.params.len() - 1, l.position()) };
+        let (me, at) = { let mut l = live.lock().unwrap(); l.params.push(LiveParam { kind, stage: self.stages.len(), cur: gains.clone(), steps: vec![(0, gains)], rate: 0 }); (l.params.len() - 1, l.position()) };
         self.push(move |c| {
             let pos = at.load(std::sync::atomic::Ordering::Relaxed);
             let frames = c.n / in_ch;
