@@ -15,6 +15,14 @@
  *     stream) and returns an rh_status; nothing throws or aborts.  End of stream (`None`) is
  *     expressed through returned lengths, never through an error.
  *   - One handle is used from one thread at a time (mirrors `Send + !Sync`).
+ *   - The one-row entries (rh_convert_*, rh_wav_decode*, rh_channels_convert, rh_amplify .. rh_take_duration_from, rh_channel_volume,
+ *     rh_amplify_steps, rh_channel_volume_steps, rh_delay, rh_echo_mix, rh_resample_linear, rh_mix_sum, rh_mix_pair, rh_noise_generate)
+ *     take rows (dst, src, a step table) at any address that is a multiple of the element size, and the sample bytes of
+ *     rh_wav_decode* at any byte address.  Their kernels may READ the aligned 16-byte vectors that hold a row's first and last
+ *     element -- up to 15 bytes either side of the row, never outside the 16 bytes that hold one of its elements, so never outside
+ *     its memory page -- and nothing read there reaches a result.  They store nothing outside dst and nothing behind the count an
+ *     entry reports (*out_samples); a call refused for its arguments (RH_ERR_INVALID, RH_ERR_UNSUPPORTED) has written nothing to
+ *     dst.  (tests/test_gpu_arena_rows.py, tests/test_gpu_arena_formats.py: every row between NaN poison or two byte fills.)
  *   - There is NO CPU fallback: without a usable HIP device rh_init() fails and every other
  *     call returns RH_ERR_NOT_INITIALIZED / RH_ERR_HIP.
  */
@@ -148,7 +156,8 @@ size_t rh_wav_header_f32_host(uint8_t *out, size_t cap, uint32_t channels, uint3
 rh_status rh_channels_convert(float *dst, const float *src, size_t frames, uint32_t from_ch,
                               uint32_t to_ch, rh_stream stream);
 
-/* ---- Amplify: src/source/amplify.rs:64 */
+/* ---- Amplify: src/source/amplify.rs:64.  dst == src works in place (as for rh_distortion, rh_dither and rh_linear_gain_ramp:
+ * a lane reads its four samples before it stores them, and stores no others). */
 rh_status rh_amplify(float *dst, const float *src, size_t n, float factor, rh_stream stream);
 
 /* ---- Distortion: src/source/distortion.rs:66-72.  threshold < 0 or NaN: RH_ERR_INVALID (f32::clamp panics). */
@@ -169,7 +178,8 @@ rh_status rh_linear_gain_ramp(float *dst, const float *src, size_t n, uint64_t s
                               uint32_t sample_rate, uint64_t duration_ns, float start_gain, float end_gain,
                               int32_t clamp_end, rh_stream stream);
 
-/* ---- Delay: src/source/delay.rs:8-16,68-75: rh_delay_samples() zeros, then the n input samples (dst holds both). */
+/* ---- Delay: src/source/delay.rs:8-16,68-75: rh_delay_samples() zeros, then the n input samples (dst holds both).
+ * n == 0: src is not read and may be NULL (the same for rh_echo_mix). */
 rh_status rh_delay(float *dst, const float *src, uint64_t n, uint64_t delay_samples, rh_stream stream);
 /* ---- TakeDuration (+ its fade-out filter): src/source/take.rs:96-148.  src holds n samples of the stream that
  * start at sample_offset; dst (capacity n + channels) receives *out_samples: the samples the duration
@@ -181,13 +191,16 @@ rh_status rh_take_duration(float *dst, const float *src, uint64_t n, uint64_t sa
 /* ... the same from ANY state of the adapter (after `try_seek`, take.rs:222-231: remaining = requested.saturating_sub(pos), the frame
  * position 0): remaining_ns = what is left of the duration at src[0], requested_ns = the adapter's whole duration (the fade-out
  * filter's denominator, :33-38), frame_phase = samples of the current frame already emitted (decides the silence that completes
- * a cut frame, :107-115).  *remaining_after_ns (may be NULL) = what is left behind the samples taken. */
+ * a cut frame, :107-115).  *remaining_after_ns (may be NULL) = what is left behind the samples taken.  Where no sample is
+ * taken (n == 0, or remaining_ns below one sample: only the zeros that complete the frame are written) src is not read and may
+ * be NULL.  RH_ERR_INVALID: frame_phase >= channels, out_samples == NULL, zero channels or rate. */
 rh_status rh_take_duration_from(float *dst, const float *src, uint64_t n, uint64_t remaining_ns, uint64_t requested_ns,
                                 uint32_t frame_phase, uint32_t channels, uint32_t sample_rate, int32_t fade_out,
                                 uint64_t *out_samples, int32_t *ended, uint64_t *remaining_after_ns, rh_stream stream);
 
 /* ---- ChannelVolume / Spatial: src/source/channel_volume.rs:71-88, src/source/spatial.rs:48-69.
- * gains_host has out_ch entries (out_ch <= 16).  dst holds frames*out_ch samples. */
+ * gains_host has out_ch entries (out_ch <= 16; more: RH_ERR_UNSUPPORTED).  dst holds frames*out_ch samples; dst == src works
+ * in place where in_ch == out_ch. */
 rh_status rh_channel_volume(float *dst, const float *src, size_t frames, uint32_t in_ch,
                             const float *gains_host, uint32_t out_ch, rh_stream stream);
 /* Host-side: gains[2] from emitter / ear positions (spatial.rs:48-69). */
@@ -358,7 +371,8 @@ rh_status rh_echo_flush(rh_echo *p, float *dst, rh_stream stream);
  * sources in insertion order (bit-identical rounding sequence).  Source s contributes samples
  * [start[s], start[s]+len[s]) (start = frame-aligned admission, mixer.rs:175-183).
  * srcs_host / start_host / len_host are host arrays of n_sources entries; dst holds out_len
- * samples = max(start+len). */
+ * samples = max(start+len).  A source of len 0 is not read and may be NULL; n_sources == 0 writes out_len zeros; a source
+ * that runs past out_len is clipped.  The sum is never -0.0 (it starts at +0.0). */
 rh_status rh_mix_sum(float *dst, size_t out_len, const float *const *srcs_host,
                      const uint64_t *start_host, const uint64_t *len_host, uint32_t n_sources,
                      rh_stream stream);

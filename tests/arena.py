@@ -7,13 +7,24 @@ read outside a row that reaches the arithmetic comes out as NaN instead of as `j
 back: every guard and gap word must still be the sentinel (nothing stored outside a row) and every row word must differ from it (nothing
 left unwritten), except behind the count an entry reports (`*out_n` of rh_chirp, the samples a take admits), where it must still be there.
 
-The layouts and `check` are pure numpy (tests/test_arena_cpu.py holds them on arrays spoiled by hand); only `Arena` touches torch."""
+Rows of 1-, 2- and 8-byte elements, and sample bytes at any byte address (`file + data_offset`), lie in BYTE layouts: the row `lead` bytes
+(0..15) behind a 16-byte boundary, GUARD_BYTES of one byte value in front and behind.  Integers have no NaN, so those arenas come in PAIRS,
+one per value of FILLS (two bytes that differ in every bit).  A source between fills: the call runs under both, each output equals the
+reference and the two outputs equal each other bit for bit (`same_under_fills`) -- a row that takes anything from its surroundings differs
+under one of them.  A destination between fills (`check_filled`): under each fill every guard and gap byte is untouched and the row equals
+the reference -- an element that was never written still holds the fill, which equals the reference under at most one of the two.
+
+The layouts and the checkers are pure numpy (tests/test_arena_cpu.py holds them on arrays spoiled by hand); only `Arena` and `ByteArena`
+touch torch."""
 import numpy as np
 
 GUARD = 1024  # words in front of the first row and behind the last one: a multiple of 4, wider than any vector or tile tail
 SENTINEL = 0x7FC5A5A5  # quiet NaN, payload 0x5a5a5: what an output arena holds before the call
 POISON = 0x7FC00BAD  # quiet NaN, another payload: what surrounds a source
 INT_SENTINEL = 0x80000001  # for integer rows: a value the tests' data cannot produce (function codes, small counters)
+GUARD_BYTES = 4 * GUARD  # the same zones in a byte layout
+FILLS = (0x55, 0xAA)  # the two surroundings of an integer row: every bit differs, so no element of any size equals both
+NAN_FILL = 0xFF  # a byte whose repetition is a NaN at every byte shift of a float (0xffffffff): around f32 sample bytes at odd addresses
 
 
 class Layout:
@@ -175,17 +186,20 @@ def state_arena(k, init=None):
     return Arena(layout(k, 0, SENTINEL), [v])
 
 
-def plain(x, rows=1, stride=None):
-    """The same rows in friendly surroundings, for the bit comparisons of arena against plain runs: zeros around and between the sources."""
+def plain(x, rows=1, stride=None, lead=0):
+    """The same rows in friendly surroundings, for the bit comparisons of arena against plain runs: zeros around and between the sources.
+    lead: elements (of x's type) the first row lies behind a 16-byte boundary, as in the arena run it is compared with."""
     import torch
 
     xs = np.ascontiguousarray(x).reshape(rows, -1)
     stride = stride or xs.shape[1]
-    buf = np.zeros(GUARD + rows * stride + GUARD, dtype=xs.dtype)
+    assert (GUARD * xs.dtype.itemsize) % 16 == 0 and 0 <= lead * xs.dtype.itemsize < 16
+    buf = np.zeros(GUARD + lead + rows * stride + GUARD, dtype=xs.dtype)
     for r in range(rows):
-        buf[GUARD + r * stride: GUARD + r * stride + xs.shape[1]] = xs[r]
+        buf[GUARD + lead + r * stride: GUARD + lead + r * stride + xs.shape[1]] = xs[r]
     t = torch.from_numpy(buf).cuda()
-    return t, t.data_ptr() + GUARD * xs.dtype.itemsize
+    assert t.data_ptr() % 16 == 0
+    return t, t.data_ptr() + (GUARD + lead) * xs.dtype.itemsize
 
 
 def plain_dst(n_words):
@@ -194,3 +208,137 @@ def plain_dst(n_words):
 
     t = torch.zeros(n_words + 8, dtype=torch.float32, device="cuda")
     return t, t.data_ptr()
+
+
+# ---- rows of any element size: byte layouts, two fills ----------------------------------------------------------------------------------
+class ByteLayout:
+    """Where the rows lie in a buffer of `total` BYTES: row r covers bytes [starts[r], starts[r] + n); everything else holds the byte `fill`."""
+
+    def __init__(self, total, starts, n, fill):
+        self.total, self.starts, self.n, self.fill = int(total), [int(s) for s in starts], int(n), int(fill)
+        assert 0 <= self.fill <= 255
+
+    @property
+    def rows(self):
+        return len(self.starts)
+
+
+def layout_bytes_rows(S, nbytes, stride, lead=0, fill=FILLS[0]):
+    """S rows of nbytes bytes, `stride` bytes apart, the first one `lead` bytes (0..15) behind a 16-byte boundary."""
+    assert S >= 1 and nbytes >= 0 and stride >= nbytes and 0 <= lead < 16 and GUARD_BYTES % 16 == 0
+    span = (S - 1) * stride + nbytes
+    return ByteLayout(GUARD_BYTES + lead + span + GUARD_BYTES, [GUARD_BYTES + lead + r * stride for r in range(S)], nbytes, fill)
+
+
+def layout_bytes(nbytes, lead=0, fill=FILLS[0]):
+    return layout_bytes_rows(1, nbytes, nbytes, lead, fill)
+
+
+def as_bytes(x):
+    """The bytes of an array of any element type, as they lie in memory."""
+    return np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+
+
+def build_bytes(lay, rows=None):
+    """The bytes of a fresh arena: `fill` everywhere, row r = the bytes of rows[r] where rows are given."""
+    b = np.full(lay.total, lay.fill, dtype=np.uint8)
+    if rows is not None:
+        assert len(rows) == lay.rows
+        for s, x in zip(lay.starts, rows):
+            x = as_bytes(x)
+            assert x.size == lay.n
+            b[s: s + lay.n] = x
+    return b
+
+
+def _where_bytes(lay, i):
+    r = max([k for k, s in enumerate(lay.starts) if s <= i], default=0)
+    return f"byte offset {i - lay.starts[r]:+d} relative to row {r} (rows of {lay.n} bytes)"
+
+
+def check_filled(host_bytes, lay, ref_rows, written=None):
+    """host_bytes: a byte arena after the call (uint8).  ref_rows: what row r must hold, any element type, lay.n bytes each (one array for
+    one row).  written: BYTES of each row the entry's contract says it writes (None = all); behind them the fill must still be there.
+    Every guard and gap byte must hold the fill and every row must equal its reference.  An element that was never written holds the fill:
+    run the call under both FILLS and it differs from the reference under at least one.  Returns the rows' bytes (a copy)."""
+    b = np.asarray(host_bytes)
+    assert b.dtype == np.uint8 and b.ndim == 1 and b.size == lay.total, "check_filled() wants the arena's bytes"
+    refs = [ref_rows] if lay.rows == 1 and not isinstance(ref_rows, (list, tuple)) else list(ref_rows)
+    counts = [lay.n] * lay.rows if written is None else ([int(written)] * lay.rows if np.isscalar(written) else [int(c) for c in written])
+    assert len(refs) == lay.rows and len(counts) == lay.rows and all(0 <= c <= lay.n for c in counts)
+    may_write = np.zeros(lay.total, dtype=bool)
+    for s, c in zip(lay.starts, counts):
+        may_write[s: s + c] = True
+    stored = np.flatnonzero(~may_write & (b != np.uint8(lay.fill)))
+    if stored.size:
+        i = int(stored[0])
+        raise AssertionError(f"stored outside what the entry may write: {stored.size} byte(s), the first at {_where_bytes(lay, i)}: 0x{int(b[i]):02x} (fill 0x{lay.fill:02x})")
+    for r, (s, c, ref) in enumerate(zip(lay.starts, counts, refs)):
+        ref = as_bytes(ref)
+        assert ref.size >= c, "the reference is shorter than what the entry writes"
+        bad = np.flatnonzero(b[s: s + c] != ref[:c])
+        if bad.size:
+            i = int(bad[0])
+            held = "it still holds the fill (never written?)" if b[s + i] == lay.fill else f"0x{int(b[s + i]):02x}"
+            raise AssertionError(f"row {r} differs from the reference in {bad.size} byte(s) under fill 0x{lay.fill:02x}, the first at byte {i}: {held}, reference 0x{int(ref[i]):02x}")
+    out = np.stack([b[s: s + lay.n] for s in lay.starts]).copy()
+    return out[0] if lay.rows == 1 else out
+
+
+def same_under_fills(outs, ref, tol=0.0, fills=FILLS):
+    """outs: the output rows of the same call with its integer source between each of `fills` (any element type).  Each must equal the
+    reference -- as bytes (a NaN equals itself only bit for bit), or for an entry that is held by a tolerance within `tol` of it (a NaN
+    is outside) -- and they must equal each other as bytes."""
+    assert len(outs) == len(fills) == 2
+    r = as_bytes(ref)
+    bs = [as_bytes(o) for o in outs]
+    for fill, o, out in zip(fills, bs, outs):
+        assert o.size == r.size, "an output of another length than the reference"
+        if tol:
+            err = np.abs(np.asarray(out, np.float64).reshape(-1) - np.asarray(ref, np.float64).reshape(-1))
+            bad = np.flatnonzero(~(err <= tol))
+        else:
+            bad = np.flatnonzero(o != r)
+        assert bad.size == 0, f"differs from the reference with 0x{fill:02x} around the source: {bad.size} {'value' if tol else 'byte'}(s), the first at {'index' if tol else 'byte'} {int(bad[0])}"
+    bad = np.flatnonzero(bs[0] != bs[1])
+    assert bad.size == 0, f"the row depends on its surroundings: {bad.size} byte(s) differ between the two fills, the first at byte {int(bad[0])}"
+
+
+class ByteArena:
+    """A byte layout on the device; the same calls as Arena.  check(ref_rows) is check_filled on the bytes copied back."""
+
+    def __init__(self, lay, rows=None):
+        import torch
+
+        self.layout = lay
+        self.initial = build_bytes(lay, rows)
+        self.buf = torch.from_numpy(self.initial.copy()).cuda()
+        assert self.buf.data_ptr() % 16 == 0
+
+    def ptr(self, r=0):
+        return self.buf.data_ptr() + self.layout.starts[r]
+
+    def bytes(self):
+        import torch
+
+        torch.cuda.synchronize()
+        return self.buf.cpu().numpy()
+
+    def check(self, ref_rows, written=None, dtype=np.uint8):
+        return check_filled(self.bytes(), self.layout, ref_rows, written).view(dtype)
+
+    def unchanged(self):
+        b = self.bytes()
+        bad = np.flatnonzero(b != self.initial)
+        assert bad.size == 0, f"a read-only arena was written: {bad.size} byte(s), the first at {_where_bytes(self.layout, int(bad[0]))}"
+
+
+def src_bytes_arena(x, lead=0, fill=FILLS[0]):
+    """x (any element type) between two zones of the byte `fill`, `lead` BYTES behind a 16-byte boundary."""
+    x = as_bytes(x)
+    return ByteArena(layout_bytes(x.size, lead, fill), [x])
+
+
+def dst_bytes_arena(n, dtype, lead=0, fill=FILLS[0]):
+    """n elements of `dtype` between zones of the byte `fill` (the row itself holds it too), `lead` BYTES behind a 16-byte boundary."""
+    return ByteArena(layout_bytes(n * np.dtype(dtype).itemsize, lead, fill))

@@ -108,6 +108,136 @@ def test_a_scratch_arena_is_held_by_its_guards_alone():
         arena.check_guards(w, lay)
 
 
+# ---- byte layouts and the two fills (rows of 1-, 2- and 8-byte elements, sample bytes at any byte address) -----------------------------
+def _ref_rows(lay, dtype):
+    """What a well-behaved kernel leaves in the rows: values that hold neither fill byte."""
+    k = lay.n // np.dtype(dtype).itemsize
+    return [(np.arange(k) % 61 + 1 + r).astype(dtype) for r in range(lay.rows)]
+
+
+def _after(lay, refs):
+    return arena.build_bytes(lay, refs)
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.int16, np.int32, np.int64, np.float64])
+def test_byte_layouts_put_rows_at_every_byte_lead(dtype):
+    assert arena.GUARD_BYTES == 4 * arena.GUARD and all(((arena.FILLS[0] ^ arena.FILLS[1]) >> k) & 1 for k in range(8))
+    assert all(np.isnan(np.full(7, arena.NAN_FILL, np.uint8)[s: s + 4].copy().view(np.float32)[0]) for s in range(4))
+    size = np.dtype(dtype).itemsize
+    for lead in range(16):
+        for fill in arena.FILLS:
+            lay = arena.layout_bytes(1001 * size, lead, fill)
+            assert lay.starts[0] % 16 == lead and lay.starts[0] >= arena.GUARD_BYTES and lay.total - (lay.starts[0] + lay.n) >= arena.GUARD_BYTES
+            refs = _ref_rows(lay, dtype)
+            b = arena.build_bytes(lay, refs)
+            assert np.all(b[: lay.starts[0]] == fill) and np.all(b[lay.starts[0] + lay.n:] == fill)
+            row = arena.check_filled(b, lay, refs[0])
+            assert row.dtype == np.uint8 and np.array_equal(row.view(dtype), refs[0])
+    lay = arena.layout_bytes_rows(3, 2002, 2050, lead=7)
+    assert [s - lay.starts[0] for s in lay.starts] == [0, 2050, 4100] and lay.starts[0] % 16 == 7
+    assert arena.check_filled(_after(lay, _ref_rows(lay, np.int16)), lay, _ref_rows(lay, np.int16)).shape == (3, 2002)
+
+
+@pytest.mark.parametrize("fill", arena.FILLS)
+def test_one_byte_stored_directly_in_front_of_a_byte_row(fill):
+    lay = arena.layout_bytes(2 * 1001, lead=5, fill=fill)
+    refs = _ref_rows(lay, np.int16)
+    b = _after(lay, refs)
+    b[lay.starts[0] - 1] = 0
+    with pytest.raises(AssertionError, match=r"stored outside.*byte offset -1 relative to row 0"):
+        arena.check_filled(b, lay, refs[0])
+
+
+@pytest.mark.parametrize("fill", arena.FILLS)
+def test_one_byte_stored_directly_behind_a_byte_row(fill):
+    lay = arena.layout_bytes(8 * 1001, lead=8, fill=fill)
+    refs = _ref_rows(lay, np.float64)
+    b = _after(lay, refs)
+    b[lay.starts[0] + lay.n] ^= 0x01  # one bit of the byte behind the last f64
+    with pytest.raises(AssertionError, match=r"stored outside.*byte offset \+8008 relative to row 0"):
+        arena.check_filled(b, lay, refs[0])
+
+
+def test_one_byte_stored_in_the_gap_between_byte_rows():
+    lay = arena.layout_bytes_rows(3, 1001, 1024, lead=3)
+    refs = _ref_rows(lay, np.uint8)
+    b = _after(lay, refs)
+    b[lay.starts[1] + 1010] = 0
+    with pytest.raises(AssertionError, match=r"stored outside.*byte offset \+1010 relative to row 1"):
+        arena.check_filled(b, lay, refs)
+
+
+def test_a_byte_stored_behind_a_reported_count_of_bytes():
+    lay = arena.layout_bytes(4 * 100, lead=4)
+    ref = (np.arange(100) + 1).astype(np.int32)
+    b = arena.build_bytes(lay)
+    b[lay.starts[0]: lay.starts[0] + 4 * 61] = arena.as_bytes(ref[:61])
+    arena.check_filled(b, lay, ref, written=4 * 61)
+    with pytest.raises(AssertionError, match=r"stored outside.*byte offset \+240 relative to row 0"):
+        arena.check_filled(b, lay, ref, written=4 * 60)
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.int16, np.int64])
+def test_an_unwritten_element_whose_reference_equals_one_of_the_fills(dtype):
+    """The reference of element 500 IS fill 0 repeated: under that fill an element that was never written cannot be told from a written one,
+    under the other fill it can -- so a case that runs both fills always notices."""
+    size = np.dtype(dtype).itemsize
+    failures = 0
+    for fill in arena.FILLS:
+        lay = arena.layout_bytes(1001 * size, lead=size, fill=fill)
+        ref = _ref_rows(lay, dtype)[0]
+        ref.view(np.uint8)[500 * size: 501 * size] = arena.FILLS[0]
+        b = _after(lay, [ref])
+        b[lay.starts[0] + 500 * size: lay.starts[0] + 501 * size] = fill  # the kernel skipped element 500
+        if fill == arena.FILLS[0]:
+            arena.check_filled(b, lay, ref)  # invisible here ...
+        else:
+            with pytest.raises(AssertionError, match=rf"row 0 differs from the reference.*first at byte {500 * size}: it still holds the fill"):
+                arena.check_filled(b, lay, ref)  # ... and caught here
+            failures += 1
+    assert failures == 1
+
+
+def test_a_wrong_value_in_a_byte_row():
+    lay = arena.layout_bytes(2 * 1001, lead=2)
+    refs = _ref_rows(lay, np.int16)
+    b = _after(lay, refs)
+    b[lay.starts[0] + 2 * 777] ^= 0x80
+    with pytest.raises(AssertionError, match=r"row 0 differs from the reference in 1 byte\(s\).*first at byte 1554"):
+        arena.check_filled(b, lay, refs[0])
+
+
+def test_a_row_that_depends_on_its_surroundings():
+    ref = np.linspace(-1, 1, 1001).astype(np.float32)
+    arena.same_under_fills([ref.copy(), ref.copy()], ref)
+    a, b = ref.copy(), ref.copy()
+    a[1000] = np.float32(arena.FILLS[0]) / np.float32(128)  # the last sample took a byte from behind the source, under both fills
+    b[1000] = np.float32(arena.FILLS[1]) / np.float32(128)
+    with pytest.raises(AssertionError, match="differs from the reference with 0x55 around the source"):
+        arena.same_under_fills([a, b], ref)
+    with pytest.raises(AssertionError, match="differs from the reference with 0xaa around the source"):
+        arena.same_under_fills([ref.copy(), b], ref)
+    # an entry that is held to its reference by a tolerance: both outputs are inside it, and only their comparison can tell
+    a[1000], b[1000] = ref[1000] + np.float32(2e-6), ref[1000] - np.float32(2e-6)
+    with pytest.raises(AssertionError, match=r"depends on its surroundings: \d byte\(s\) differ.*first at byte 4000"):
+        arena.same_under_fills([a, b], ref, tol=1e-5)
+    arena.same_under_fills([a, a.copy()], ref, tol=1e-5)
+    a[3] = np.nan
+    with pytest.raises(AssertionError, match="differs from the reference with 0x55"):
+        arena.same_under_fills([a, a.copy()], ref, tol=1e-5)  # a NaN is outside every tolerance
+
+
+def test_check_filled_wants_the_bytes_it_was_built_for():
+    lay = arena.layout_bytes(64)
+    refs = _ref_rows(lay, np.uint8)
+    with pytest.raises(AssertionError):
+        arena.check_filled(_after(lay, refs).view(np.uint32), lay, refs[0])
+    with pytest.raises(AssertionError):
+        arena.check_filled(_after(lay, refs)[:-1], lay, refs[0])
+    with pytest.raises(AssertionError):
+        arena.same_under_fills([refs[0]], refs[0])
+
+
 def test_same_compares_bits_and_flattens():
     a = np.array([[0.0, np.nan], [1.0, -0.0]], np.float32)
     assert arena.same(a, a.reshape(-1)) and not arena.same(a, -a) and not arena.same(a[0], a)
