@@ -17,7 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "librodio_hip.so")
-SOURCES = ["rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_limit.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip", "rh_generators.hip", "rh_noise.hip", "rh_mix2.hip"]
+# (the units that take longest to compile come first: the pool never starts a long pole last)
+SOURCES = ["rh_pipeline_wave.hip", "rh_limit.hip", "rh_pipeline_fast_hi.hip", "rh_pipeline_fast_lo.hip", "rh_pipeline_fast1.hip",
+           "rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_chunk.hip", "rh_pipeline_mix.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip", "rh_generators.hip", "rh_noise.hip", "rh_mix2.hip"]
 # -ffp-contract=off: the reference's f32 expressions (lerp, biquad, mixer sum) must not be
 # fused; kernels that want an FMA spell it __builtin_fmaf.
 # -fno-slp-vectorize: hipcc's SLP pass pairs the two stereo channels into v_pk_*_f32; on gfx950
@@ -59,7 +61,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4) or 1) as ex:
+    # MAX_JOBS, where it is set, says how many CPUs this build may use; a machine's own count can be many times that
+    workers = int(os.environ.get("MAX_JOBS") or 0) or min(os.cpu_count() or 4, 16)
+    with ThreadPoolExecutor(max_workers=min(len(jobs), workers) or 1) as ex:
         list(ex.map(run, jobs))
     if force or jobs or _stale(LIB, objs):
         run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs, "-ldl"])

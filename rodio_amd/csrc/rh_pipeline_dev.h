@@ -1,5 +1,6 @@
-// rh_pipeline_dev.h -- device-side helpers the kernels of the fused path share (rh_pipeline.hip: k_rlm_fast / k_rlm_wave / k_rlm_chunk /
-// k_mix_*; rh_pipeline_sblk.hip: k_rlm_sblk): the converter's cursor, the lane primitives (rh_lanes.h), the hand-counted LDS-DMA pipeline, the
+// rh_pipeline_dev.h -- device-side helpers the kernel units of the fused path share (rh_rlm_fast.h: k_rlm_fast / k_rlm_resid, instantiated by
+// rh_pipeline_fast_lo / _fast_hi / _fast1 / _wave.hip; rh_pipeline_wave.hip: k_rlm_wave; rh_pipeline_chunk.hip: k_rlm_chunk*; rh_pipeline_mix.hip: k_mix_* /
+// k_rlm_state*; rh_pipeline_sblk.hip: k_rlm_sblk): the converter's cursor, the lane primitives (rh_lanes.h), the hand-counted LDS-DMA pipeline, the
 // channel-count helpers, the state scan / tile aggregate / carry sum / tile store behind the source loops.  Not part of the C ABI.  Everything sits in an unnamed namespace: every unit gets its own copies.
 #pragma once
 #include "rh_pipeline_internal.h"

@@ -1,6 +1,7 @@
-// rh_pipeline_internal.h -- what the translation units of the fused path share (rh_pipeline.hip: the kernels, their instances and
-// the launch; rh_pipeline_plan.hip: handles, plans, tables, the one-shot entry points; rh_pipeline_stream.hip: block streaming).
-// Not part of the C ABI: nothing outside rodio_amd/csrc/rh_pipeline*.hip includes it.
+// rh_pipeline_internal.h -- what the translation units of the fused path share (rh_pipeline.hip: the map of the path and the launch;
+// rh_pipeline_fast_lo / _fast_hi / _fast1 / _wave / _chunk / _mix / _sblk.hip: one kernel family each, with its instances, over rh_pipeline_dev.h;
+// rh_pipeline_plan.hip: handles, plans, tables, the one-shot entry points; rh_pipeline_stream.hip: block streaming).
+// Not part of the C ABI: nothing outside rodio_amd/csrc/rh_pipeline*.hip (and the device headers they include) includes it.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -343,23 +344,38 @@ struct rh_rlm {
 };
 
 namespace rhp {
+// The kernel units give their instance tables out through functions (never as arrays another unit could read while it initialises its own):
+VariantTab tab_fast_lo(), tab_fast_hi();  // rh_pipeline_fast_lo.hip / _hi.hip: k_rlm_fast, stereo, R <= 9 / R >= 10
+VariantTab tab_fast1();                 // rh_pipeline_fast1.hip: k_rlm_fast, mono
+VariantTab tab_wave(), tab_wave1();     // rh_pipeline_wave.hip: k_rlm_wave, stereo / mono
+VariantTab tab_rag(), tab_rag1();       // ... and k_rlm_fast<RAG> + k_rlm_resid, stereo / mono
 // rh_pipeline.hip
 enum TabKind { kTabFast, kTabWave, kTabRag };
 VariantTab variant_tab(TabKind kind, bool mono);             // the instances of k_rlm_fast / k_rlm_wave / k_rlm_fast<RAG> + k_rlm_resid
+// rh_pipeline_chunk.hip
 const void *chunk_kernel(int R, uint32_t channels, int KV);  // the instance of k_rlm_chunk, or nullptr
+// k_rlm_chunk for the batch that is set, `k` being the launch_params of the run
+rh_status launch_chunk(rh_rlm *p, Params &k, hipStream_t s);
 // The classes of a mixer with per-source filters as ONE launch of k_rlm_chunk_multi (class k's mix into rows[k]): *taken = false and nothing
 // done when a class does not take the k_rlm_chunk path, the classes' instances differ, or there are more than fit one kernarg segment
 // (*summed: the launch added the classes' mixes itself, into dst_sum -- k_rlm_chunk_classes; the rows are then unwritten)
 rh_status chunk_launch_classes(rh_rlm *const *classes, float *const *rows, uint64_t row_capacity_frames, uint32_t n, float *dst_sum, rh_stream stream, bool *taken, bool *summed);
+// rh_pipeline_mix.hip
+// Mix first: sums the sources of `k` at the input rate (k_mix_rows / k_mix_ring; pre: then filters the sum there) and turns `k` into the fused
+// launch over that one stream
+rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const StreamArgs &sa, rh_stream stream);
 // k_rlm_state on `s`: folds a block's aggregates into column 0 of the per-source rows (see rh_pipeline_stream.hip)
 void launch_state(hipStream_t s, unsigned long long *gran, const Tables *tabs, uint32_t n_sources, uint32_t cols, uint32_t last_col, uint32_t J, uint32_t epoch, uint32_t next_epoch);
 // k_rlm_state_sum on `s`: the sum of the live sources' states (column 0 of their rows, tagged `tag`) -> the 4 words of a summed state
 void launch_state_sum(hipStream_t s, const unsigned long long *gran, const SrcDesc *srcs, uint32_t n_sources, uint32_t cols, uint32_t tag, float *w_out);
+// rh_pipeline.hip
 // The facts rh::rlm::route reads, for a whole one-shot run of the handle's sources on plan `pl`; the callers set what differs (first, count,
 // batch_streams, the stream's mode and gran_cols)
 rh::rlm::RouteIn route_in(const rh_rlm *p, const Plan &pl);
 // What every launch of the fused kernels takes from the handle: the control words, the rates, the epoch and the stream's block
 void params_common(const rh_rlm *p, const StreamArgs &sa, Params &k);
+// The arguments of a launch of the active plan's kernel over sources [first, first + count)
+Params launch_params(const rh_rlm *p, const Plan &pl, uint32_t first, uint32_t count, float *dst, uint32_t batch_streams, uint64_t out_stride, const StreamArgs &sa);
 rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint64_t out_capacity_frames, uint64_t *out_frames, rh_stream stream, uint32_t batch_streams, uint64_t out_stride_floats,
                      const StreamArgs &sa = StreamArgs());
 // rh_pipeline_sblk.hip: a block of a stream on the summed state in ONE launch (k_rlm_sblk); *taken = false: not this kernel's block

@@ -1,4 +1,4 @@
-// rh_pipeline_plan.hip -- the host side of the fused path (rh_pipeline.hip has the kernels and the launch): handles, launch plans and
+// rh_pipeline_plan.hip -- the host side of the fused path (rh_pipeline.hip has the launch and the map of the kernel units): handles, launch plans and
 // their tables, the sources / gains / filter classes of a batch, the one-shot entry points, the tuner and the diagnostics.
 #include "rh_pipeline_internal.h"
 

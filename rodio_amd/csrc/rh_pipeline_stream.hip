@@ -1,5 +1,5 @@
 // rh_pipeline_stream.hip -- block streaming of the fused path: the state that crosses a block boundary and the launches of a block
-// (the kernels and rlm_launch: rh_pipeline.hip; handles and plans: rh_pipeline_plan.hip).
+// (rlm_launch and the map of the kernel units: rh_pipeline.hip; handles and plans: rh_pipeline_plan.hip).
 #include "rh_pipeline_internal.h"
 
 extern "C" {

@@ -36,12 +36,14 @@ def code_objects():
         pos = i + len(MAGIC)
 
 
-def kernel_metadata(tmp_path):
+def kernel_metadata(tmp_path, per_object=None):
+    """name -> fields of every kernel of the library; per_object (a list), if given, also receives the names of each code object, in order."""
     kernels = {}
     for n, img in enumerate(code_objects()):
         f = tmp_path / f"co_{n}.elf"
         f.write_bytes(img)
         txt = subprocess.run([READELF, "--notes", str(f)], capture_output=True, text=True, check=True).stdout
+        names = []
         for block in txt.split("- .agpr_count:")[1:]:  # one metadata map per kernel (keys are sorted: .agpr_count comes first)
             name = re.search(r"\.name:\s+(\S+)", block)
             if not name:
@@ -49,6 +51,9 @@ def kernel_metadata(tmp_path):
             fields = {k: int(v) for k, v in re.findall(r"\.(private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count|sgpr_count|group_segment_fixed_size):\s+(\d+)", block)}
             fields["dynamic_stack"] = bool(re.search(r"\.uses_dynamic_stack:\s+true", block))
             kernels[name.group(1)] = fields
+            names.append(name.group(1))
+        if per_object is not None:
+            per_object.append(names)
     return kernels
 
 
@@ -73,6 +78,33 @@ def test_the_agc_kernel_of_round_5_keeps_its_twelve_waves(tmp_path):
     v = ks[name]
     assert v["vgpr_count"] <= 168, v
     assert not v.get("sgpr_spill_count", 0), v
+
+
+FUSED_FAMILIES = {  # instances per kernel of the fused path: the units' tables (rh_pipeline_fast_lo / _fast_hi / _fast1 / _wave / _chunk / _mix.hip), 280 in all
+    "k_rlm_fast": 183, "k_rlm_resid": 16, "k_rlm_wave": 60,
+    "k_rlm_chunk": 5, "k_rlm_chunk_multi": 5, "k_rlm_chunk_classes": 4,
+    "k_mix_rows": 3, "k_mix_ring": 2, "k_rlm_state": 1, "k_rlm_state_sum": 1,
+}
+
+
+@pytest.mark.skipif(not os.path.exists(READELF), reason="llvm-readelf not found")
+def test_every_kernel_lives_in_one_code_object_and_the_fused_families_are_whole(tmp_path):
+    """The fused path is one translation unit per kernel family, several of them over one header of kernel text (rh_rlm_fast.h): an instance
+    that two units instantiate would be compiled and loaded twice, and one that a cut of a table dropped would be missed only when its shape
+    is asked for."""
+    per_object = []
+    ks = kernel_metadata(tmp_path, per_object)
+    names = [k for obj in per_object for k in obj]
+    assert len(names) > 100, len(names)
+    twice = sorted({k for k in names if names.count(k) > 1})
+    assert not twice, twice
+    assert len(ks) == len(names)
+    if "RH_DEV_VARIANTS" in os.environ.get("RH_EXTRA_HIPCC_FLAGS", ""):
+        return  # a development build carries a short table of k_rlm_fast: the counts below are the full library's
+    # a name is counted by its mangled identifier, length in front: "11k_rlm_chunk" is not part of "17k_rlm_chunk_multi"
+    got = {fam: sum(1 for k in names if re.search(r"%d%s(?![a-z0-9_])" % (len(fam), fam), k)) for fam in FUSED_FAMILIES}
+    assert got == FUSED_FAMILIES, got
+    assert sum(got.values()) == 280
 
 
 OBJDUMP = shutil.which("llvm-objdump") or "/opt/rocm/lib/llvm/bin/llvm-objdump"

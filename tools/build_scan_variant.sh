@@ -7,8 +7,11 @@ cd "$(dirname "$0")/.."
 mkdir -p variants/obj_$name
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-function"
 objs=""
-for f in rh_runtime rh_elementwise rh_resample rh_recurrence rh_stream rh_uniform rh_widemix rh_formats rh_wav rh_comm rh_pipeline rh_pipeline_plan rh_pipeline_stream rh_pipeline_sblk; do objs="$objs rodio_amd/build/$f.o"; done
-for f in rh_limit rh_biquad_scan rh_agc; do
+scan="rh_limit rh_biquad_scan rh_agc"
+# the units are build.py's
+units=$(python3 -c "import runpy; print(' '.join(s[:-len('.hip')] for s in runpy.run_path('rodio_amd/build.py')['SOURCES']))")
+for f in $units; do case " $scan " in *" $f "*) ;; *) objs="$objs rodio_amd/build/$f.o" ;; esac; done
+for f in $scan; do
   /opt/rocm/bin/hipcc $FLAGS "$@" -c rodio_amd/csrc/$f.hip -o variants/obj_$name/$f.o &
   objs="$objs variants/obj_$name/$f.o"
 done
