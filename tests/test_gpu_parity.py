@@ -725,11 +725,11 @@ def test_mixer_random_ordered_sum_bit_exact(G, O, S, n):
 
 
 # ====================================================================== fused pipeline ====
-def _oracle_pipeline(O, xs, frm, to, span, filt, freq):
-    m = O.Mixer(2, to)
+def _oracle_pipeline(O, xs, frm, to, span, filt, freq, ch=2):
+    m = O.Mixer(ch, to)
     for x in xs:
-        src = O.TestSource(x, 2, frm) if not span else O.SpanSource(x, 2, frm, span)
-        u = O.UniformSourceIterator(src, 2, to)
+        src = O.TestSource(x, ch, frm) if not span else O.SpanSource(x, ch, frm, span)
+        u = O.UniformSourceIterator(src, ch, to)
         if filt == "low_pass":
             u = u.low_pass(freq)
         elif filt == "high_pass":
@@ -738,7 +738,7 @@ def _oracle_pipeline(O, xs, frm, to, span, filt, freq):
     return m.collect()
 
 
-def _truth_pipeline(O, xs, frm, to, span, filt, freq):
+def _truth_pipeline(O, xs, frm, to, span, filt, freq, ch=2):
     """f64 evaluation of the same chain on the (bit-exact) f32 resampled streams: what both the
     reference's f32 recurrence and the GPU's time-parallel evaluation approximate."""
     from scipy.signal import lfilter
@@ -746,8 +746,8 @@ def _truth_pipeline(O, xs, frm, to, span, filt, freq):
     co = O.blt_coeffs(filt, freq, 0.5, to).astype(np.float64)
     acc = None
     for x in xs:
-        src = O.TestSource(x, 2, frm) if not span else O.SpanSource(x, 2, frm, span)
-        r = O.UniformSourceIterator(src, 2, to).collect().astype(np.float64).reshape(-1, 2)
+        src = O.TestSource(x, ch, frm) if not span else O.SpanSource(x, ch, frm, span)
+        r = O.UniformSourceIterator(src, ch, to).collect().astype(np.float64).reshape(-1, ch)
         y = lfilter(co[:3], [1.0, co[3], co[4]], r, axis=0) if len(r) else r
         if acc is None or len(y) > len(acc):
             acc, y = (y.copy(), acc) if acc is not None else (y.copy(), None)
@@ -785,7 +785,8 @@ def _gpu_pipeline(G, xs, frm, to, span, filt, freq, **kw):
 
 
 # (frames per lane, ring stages, general kernel): k_rlm_fast is what equal-length batches take;
-# force_general runs the same batch through the ragged-batch kernel k_rlm_wave
+# force_general runs the same batch through the ragged-batch kernel k_rlm_wave.  A sample of the geometries at 44.1 -> 48 kHz, on larger
+# batches and three filters: test_gpu_fused_instances.py runs the full matrix, every row of the six instance tables at the rates that select it
 GEOS = [(3, 2, 0), (4, 3, 0), (5, 2, 0), (6, 3, 0), (7, 2, 0), (8, 2, 0), (8, 3, 0), (8, 4, 0), (9, 2, 0), (10, 3, 0), (12, 3, 0), (16, 3, 0),
         (6, 2, 1), (8, 2, 1), (8, 3, 1)]
 
