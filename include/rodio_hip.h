@@ -487,12 +487,29 @@ rh_status rh_biquad(float *dst, const float *src, uint64_t frames, uint32_t chan
                     uint32_t n_streams, const float coeffs5_host[5], float *state, int32_t mode,
                     rh_stream stream);
 /* THE FILTER CONTRACT.  Every time-parallel evaluation of a low_pass / high_pass in this library (rh_biquad mode 1, the fused rh_rlm_*
- * path) is CLOSER to the exact response than rodio's own f32 recurrence is, so its distance from rodio is rodio's rounding noise -- which
- * the recurrence amplifies by ~1 / (1 - r)^2 for poles of radius r.  Returns 1 where that distance stays <= 1e-5 for a FULL-SCALE source
- * (|x| <= 1; it scales with the peak): low_pass with 1 - r >= 0.0125 (>= 100 Hz at 48 kHz), high_pass with 1 - r >= 0.075 (>= 600 Hz at
- * 48 kHz); measured table: profiles/r04_filter_contract.txt.  0 outside: a drop-in for rodio's samples then takes rh_biquad mode 0 (the
- * reference's order, bit for bit) -- include/rodio_hip.hpp does so on its own (GpuSource: per filter; GpuMixer: the source gets a chain
- * amplify -> uniform -> filter in mode 0 of its own and enters the mixer unfiltered). */
+ * path, its streamed blocks) is held to two things, on noise, DC, steps, impulses, tones at the cutoff, a Nyquist alternation and tails
+ * that fall silent, through real, double and complex poles (tests/test_gpu_filter_signals.py, profiles/filter_signals.txt):
+ *   (B) it is no further from the exact (f64) response than rodio's own f32 recurrence: |scan - exact| <= 2 |rodio - exact| + F, where
+ *       F = 8 * 2^-24 * max|x| * sum|h| is a handful of f32 roundings at the size of the terms a time-parallel evaluation adds up;
+ *   (C) it is within 1e-5 * peak of rodio's samples (peak = max(1, max|y|)) wherever rodio itself is within 5e-6 * peak of the exact
+ *       response.
+ * Where rodio is further from the exact response than that, |scan - rodio| IS rodio's rounding noise, which the recurrence amplifies by
+ * ~1 / (1 - r)^2 for poles of radius r.  rh_filter_scan_ok returns 1 where that noise stays <= 1e-5 for full-scale WHITE NOISE
+ * (|x| <= 1; it scales with the peak): low_pass with 1 - r >= 0.0125 (>= 100 Hz at 48 kHz), high_pass with 1 - r >= 0.075 (>= 600 Hz
+ * at 48 kHz); measured table: profiles/r04_filter_contract.txt.  On DC-heavy material through a low cutoff rodio's recurrence is biased
+ * by more than that although the filter passes: |rodio - exact| at 48 kHz, one channel, 24 000 frames --
+ *       filter                    noise      DC 1.0     tone at the cutoff
+ *       low_pass  100, q 0.5      6.3e-6     3.1e-4     1.8e-5
+ *       low_pass  200, q 0.5      2.1e-6     6.5e-5     6.3e-6
+ *       low_pass  300, q 0.35     9.8e-7     1.1e-5     3.2e-6
+ *       low_pass  800, q 2.0      2.7e-6     8.4e-6     8.2e-6   (peak 2.0)
+ *       low_pass 1000, q 0.5      6.2e-7     4.0e-6     5.2e-7
+ *       low_pass 1000, q 0.7071   1.2e-6     2.0e-6     9.7e-7
+ * -- while the scan stays within 1.1e-6 of the exact response on the rows from 200 Hz up (measured on an MI355X), so on such material it differs
+ * from rodio by rodio's bias: (C) does not apply there, (B) does.  0 outside the thresholds: a drop-in for rodio's samples then takes
+ * rh_biquad mode 0 (the reference's order, bit for bit) -- include/rodio_hip.hpp does so on its own (GpuSource: per filter; GpuMixer:
+ * the source gets a chain amplify -> uniform -> filter in mode 0 of its own and enters the mixer unfiltered); a caller that needs
+ * rodio's samples on DC through a low cutoff asks for mode 0 itself (exact_filters(true)). */
 int32_t rh_filter_scan_ok(int32_t kind, uint32_t freq, float q, uint32_t sample_rate);
 
 /* ---- src/math.rs:51-56,86-90,110-113 (host): dB <-> linear as the reference spells them (2^(dB*0.05*log2 10),

@@ -1729,11 +1729,14 @@ public:
     }
     /// How the filters of this chain run.  By default (neither call) every filter decides for itself by THE FILTER CONTRACT
     /// (rodio_hip.h, rh_filter_scan_ok): time-parallel (rh_biquad mode 1) where that stays within 1e-5 of rodio's own f32
-    /// recurrence for a full-scale source, the reference's operation order (mode 0, bit for bit, one lane per channel) where it
-    /// would not -- low cutoffs, where rodio's recurrence amplifies its own rounding noise past 1e-5.  exact_filters(true): the
-    /// reference's order throughout.  exact_filters(false): time-parallel throughout -- closer to the exact response than rodio
-    /// is, further than 1e-5 from rodio at low cutoffs.  (Blocks the scan kernel does not take run in reference order on the
-    /// same state either way.)
+    /// recurrence for full-scale white noise, the reference's operation order (mode 0, bit for bit, one lane per channel) where it
+    /// would not -- low cutoffs, where rodio's recurrence amplifies its own rounding noise past 1e-5.  On every signal class the
+    /// time-parallel filter is no further from the exact response than rodio's recurrence, and within 1e-5 * peak of rodio wherever
+    /// rodio itself is within 5e-6 * peak of the exact response; rodio is not on DC-heavy material through low cutoffs (DC 1.0
+    /// through low_pass(200): 6.5e-5 from the exact response; the table in rodio_hip.h), where the two differ by rodio's bias.
+    /// exact_filters(true): the reference's order throughout -- rodio's samples on such material too.  exact_filters(false):
+    /// time-parallel throughout -- further than 1e-5 from rodio at low cutoffs.  (Blocks the scan kernel does not take run in
+    /// reference order on the same state either way.)
     GpuSource &exact_filters(bool on = true) {
         filter_mode_ = on ? 1 : 2;
         return *this;
@@ -3206,7 +3209,9 @@ public:
         unsigned host_threads = 0;            // threads that pull the sources of a block (0 = min(cores, 16); 1 = the caller alone)
         // THE FILTER CONTRACT (rodio_hip.h, rh_filter_scan_ok).  The fused kernel evaluates the filters time-parallel, which stays within
         // 1e-5 of rodio's own f32 recurrence only where that recurrence does not amplify its rounding noise past it (low_pass >= 100 Hz,
-        // high_pass >= 600 Hz at 48 kHz, full-scale sources).  true (default): a source whose filter lies outside gets a chain of its own --
+        // high_pass >= 600 Hz at 48 kHz, full-scale white noise; on DC-heavy material through low cutoffs rodio's recurrence is biased by
+        // more -- 6.5e-5 on DC 1.0 through low_pass(200) -- and the fused kernel, which stays no further from the exact response than rodio
+        // on every signal class, differs from rodio by that bias).  true (default): a source whose filter lies outside gets a chain of its own --
         // amplify -> UniformSourceIterator -> the filter in rodio's operation order, bit for bit -- and enters the mix unfiltered, on the
         // device: rodio's samples, at the price of per-source launches.  false: every filter stays in the fused kernel (closer to the
         // exact response than rodio is; at low cutoffs further than 1e-5 from rodio).

@@ -602,7 +602,8 @@ def biquad_coeffs(kind, freq, q, fs) -> np.ndarray:
 
 def filter_scan_ok(kind, freq, q, fs) -> bool:
     """The filter contract (rodio_hip.h, rh_filter_scan_ok): does the time-parallel evaluation of this low_pass / high_pass stay within
-    1e-5 of rodio's own f32 recurrence for a full-scale source?"""
+    1e-5 of rodio's own f32 recurrence for full-scale white noise?  (On DC-heavy material through low cutoffs rodio's recurrence is biased
+    by more, and the two differ by that bias: the table in rodio_hip.h.)"""
     return bool(lib.rh_filter_scan_ok(1 if kind in (1, "high_pass") else 0, int(freq), float(q), int(fs)))
 
 

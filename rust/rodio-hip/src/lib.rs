@@ -791,11 +791,13 @@ impl<I: Source> GpuSource<I> {
         self
     }
     /// How the filters of this chain run.  By default every filter decides for itself by THE FILTER CONTRACT (`rodio_hip.h`,
-    /// `rh_filter_scan_ok`): time-parallel (`rh_biquad` mode 1) where that stays within 1e-5 of rodio's own f32 recurrence for a
-    /// full-scale source, the reference's operation order (mode 0, bit for bit) where it would not -- low cutoffs, where rodio's
-    /// recurrence amplifies its own rounding noise past 1e-5.  `exact_filters(true)`: the reference's order throughout;
-    /// `exact_filters(false)`: time-parallel throughout (closer to the exact response than rodio is, further than 1e-5 from rodio at
-    /// low cutoffs).
+    /// `rh_filter_scan_ok`): time-parallel (`rh_biquad` mode 1) where that stays within 1e-5 of rodio's own f32 recurrence for
+    /// full-scale white noise, the reference's operation order (mode 0, bit for bit) where it would not -- low cutoffs, where rodio's
+    /// recurrence amplifies its own rounding noise past 1e-5.  On every signal class the time-parallel filter is no further from the
+    /// exact response than rodio's recurrence, and within 1e-5 * peak of rodio wherever rodio itself is within 5e-6 * peak of the exact
+    /// response; rodio is not on DC-heavy material through low cutoffs (DC 1.0 through `low_pass(200)`: 6.5e-5; the table in
+    /// `rodio_hip.h`), where the two differ by rodio's bias.  `exact_filters(true)`: the reference's order throughout -- rodio's samples
+    /// on such material too; `exact_filters(false)`: time-parallel throughout (further than 1e-5 from rodio at low cutoffs).
     pub fn exact_filters(mut self, on: bool) -> Self { self.filter_mode = if on { 1 } else { 2 }; self }
     /// See [`GpuMixer::prepare`]: the stream is started on the calling thread, the consumer's first `next()` finds its block waiting.
     pub fn prepare(&mut self) { self.prepare_stream(); }
@@ -1408,7 +1410,8 @@ pub struct MixerOptions {
     pub frames_per_lane: u32,        // 0 = the library's choice
     pub host_threads: u32,           // threads that pull the sources of a block (0 = min(cores, 16); 1 = the caller alone)
     /// THE FILTER CONTRACT (`rodio_hip.h`, `rh_filter_scan_ok`).  true (default): a source whose filter lies outside the region in which the
-    /// fused kernel's time-parallel filter stays within 1e-5 of rodio's own recurrence gets a chain of its own -- amplify ->
+    /// fused kernel's time-parallel filter stays within 1e-5 of rodio's own recurrence on full-scale white noise (on DC-heavy material
+    /// through low cutoffs rodio's recurrence is biased by more, and the two differ by that bias) gets a chain of its own -- amplify ->
     /// UniformSourceIterator -> the filter in rodio's operation order, bit for bit -- and enters the mix unfiltered, on the device.
     pub reference_exact_filters: bool,
 }
