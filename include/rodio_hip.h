@@ -585,6 +585,26 @@ rh_status rh_rlm_destroy(rh_rlm *p);
  * samples; *out_frames = max over sources of the resampled length. */
 rh_status rh_rlm_set_sources(rh_rlm *p, const float *const *srcs_host,
                              const uint64_t *in_frames_host, uint32_t n_sources);
+/* srcs_host[s] = device pointer of source s as interleaved signed 16-bit PCM ([in_frames_host[s]][channels] int16_t, the layout of a
+ * WAV data chunk).  Equivalent, bit for bit, to rh_convert_i16_to_f32 of every row followed by rh_rlm_set_sources (dasp's i16 -> f32,
+ * `s as f32 / 32768.0`, is exact).  The arguments follow rh_rlm_set_sources' rules, except that a row may start on any 2-byte boundary;
+ * either entry replaces what the other set; rh_rlm_set_gains and rh_rlm_set_filters work unchanged.  The sources serve the one-shot
+ * entries (rh_rlm_run, _run_subset, _run_batch, _autotune); the stream entries take f32 rows per block as before.
+ * NATIVE runs -- the kernels read the int16 rows themselves, no decoded copy exists -- are the whole one-shot runs (rh_rlm_run) of a
+ * filtered batch of equal lengths on a handle without filter_first and without rh_rlm_set_filters:
+ *   - rh_rlm_geometry_info::mix_first == 2 (k_rlm_chunk_pcm16): every row on a 16-byte boundary and a whole number of 16-byte vectors
+ *     (frames * channels % 8 == 0);
+ *   - mix_first == 1 where the rows are summed by k_mix_rows (k_mix_rows_pcm16; not k_mix_ring): every row on an 8-byte boundary, any length.
+ * Every other run -- no filter, different lengths, force_general, filter_first, rh_rlm_run_subset, rh_rlm_run_batch, per-source filters,
+ * k_mix_ring's rows, rows off those boundaries -- reads an f32 copy of the rows, which the first such run makes on its stream
+ * (rh_convert_i16_to_f32) ONCE per rh_rlm_set_sources_pcm16 and which goes when the sources are replaced or the handle is destroyed:
+ * never an error, the same bits.  RH_ERR_NOMEM (from that run; from this call on a handle with per-source filters): no memory for the copy.
+ * A stream that runs on the handle afterwards puts its own blocks in the sources' place: a one-shot run behind it returns RH_ERR_INVALID until
+ * the sources are set again. */
+rh_status rh_rlm_set_sources_pcm16(rh_rlm *p, const int16_t *const *srcs_host, const uint64_t *in_frames_host, uint32_t n_sources);
+/* *format: 0 = the sources set are f32 rows, 1 = PCM16 rows.  *native: 1 = the last one-shot run read the PCM16 rows themselves,
+ * 0 = it ran on f32 rows (f32 sources, or a converted copy of PCM16 ones). */
+rh_status rh_rlm_source_format(rh_rlm *p, int32_t *format, int32_t *native);
 /* Optional per-source Amplify factors (src/source/amplify.rs:64; Player::set_volume): source s contributes
  * gains[s] * (its converted, filtered stream).  The chain is linear, so it does not matter where in it rodio
  * applies the factor; without a filter the result stays bit-identical to amplify-then-convert.  Sources beyond

@@ -182,6 +182,8 @@ SIGNATURES = {
     "rh_rlm_create": (i32, [C.POINTER(vp), C.POINTER(RlmConfig)]),
     "rh_rlm_destroy": (i32, [vp]),
     "rh_rlm_set_sources": (i32, [vp, C.POINTER(vp), C.POINTER(u64), u32]),
+    "rh_rlm_set_sources_pcm16": (i32, [vp, C.POINTER(vp), C.POINTER(u64), u32]),
+    "rh_rlm_source_format": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "rh_rlm_run": (i32, [vp, vp, u64, C.POINTER(u64), vp]),
     "rh_filter_scan_ok": (i32, [i32, u32, f32, u32]),
     "rh_rlm_set_gains": (i32, [vp, f32p, u32]),

@@ -89,6 +89,7 @@ DRIVERS = {
     "scan_launch_test": dict(hdrs=["rh_scan_launch.h"]),  # the scan kernels' host protocol against a model of the device
     "wide_filtered_test": dict(lib=True, fake=True),
     "rlm_launch_test": dict(hdrs=["rh_rlm_launch.h"]),  # the fused path's launch decisions: route, row cut, tickets, stream-block geometry
+    "pcm16_launch_test": dict(hdrs=["rh_rlm_pcm16.h", "rh_rlm_launch.h"]),  # PCM16 sources: the rows themselves or a converted copy
 }
 
 

@@ -193,13 +193,7 @@ rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint
     if (!dst || (reinterpret_cast<uintptr_t>(dst) & 15u)) return RH_ERR_INVALID;
     if (out_capacity_frames < p->out_frames) return RH_ERR_CAPACITY;
     hipStream_t s = rh::as_stream(stream);
-    rh_status w = pre_launch(p, s);
-    if (w == RH_OK) w = next_epoch(p, s);
-    if (w != RH_OK) return w;
     const Plan &pl = *p->plan;
-    Params k = launch_params(p, pl, first, count, dst, batch_streams, out_stride, sa);
-    const uint64_t grid = (uint64_t)p->n_tiles * (batch_streams ? batch_streams : 1);
-    if (grid > 0x7fffffffull) return RH_ERR_UNSUPPORTED;
     rh::rlm::RouteIn in = route_in(p, pl);
     in.first = first;
     in.count = count;
@@ -207,13 +201,35 @@ rh_status rlm_launch(rh_rlm *p, uint32_t first, uint32_t count, float *dst, uint
     in.st_mode = sa.mode;
     in.gran_cols = sa.gran_cols;
     const rh::rlm::Route r = rh::rlm::route(in);
+    // Sources set as 16-bit PCM (one-shot runs: a stream's block brings its own f32 rows): the rows themselves where a kernel reads them
+    // (rh_rlm_pcm16.h), the converted copy -- made once -- everywhere else
+    bool pcm16 = false;
+    if (!sa.mode) {
+        if (p->pcm) {
+            if (!p->pcm_current()) return RH_ERR_INVALID;  // a stream's blocks have run on the handle since: set the sources again
+            const int ring = r == rh::rlm::kMixed ? mixed_row_cut(p, count, false, sa).ring : 0;
+            pcm16 = rh::rlm::pcm16_native({r, ring, p->cfg.channels, p->eq_frames, p->pcm_bits, false, first != 0 || count != p->n_sources}) == rh::rlm::kPcmNative &&
+                    (r != rh::rlm::kChunk || p->chunk.fn_pcm);
+            if (!pcm16 && r != rh::rlm::kUnsupported) {
+                const rh_status c = pcm_f32_ready(p, s);
+                if (c != RH_OK) return c;
+            }
+        }
+        p->last_native = pcm16 ? 1 : 0;
+    }
+    rh_status w = pre_launch(p, s);
+    if (w == RH_OK) w = next_epoch(p, s);
+    if (w != RH_OK) return w;
+    Params k = launch_params(p, pl, first, count, dst, batch_streams, out_stride, sa);
+    const uint64_t grid = (uint64_t)p->n_tiles * (batch_streams ? batch_streams : 1);
+    if (grid > 0x7fffffffull) return RH_ERR_UNSUPPORTED;
     switch (r) {
     case rh::rlm::kPair: return launch_pair(p, pl, k, (uint32_t)grid, s);
-    case rh::rlm::kChunk: return launch_chunk(p, k, s);
+    case rh::rlm::kChunk: return launch_chunk(p, k, s, pcm16);
     case rh::rlm::kUnsupported: return RH_ERR_UNSUPPORTED;  // filter_first: one-shot runs of equal-length batches (rodio_hip.h)
     case rh::rlm::kMixed:
     case rh::rlm::kMixedFiltered:
-        w = launch_mixed(p, pl, k, r == rh::rlm::kMixedFiltered, sa, stream);
+        w = launch_mixed(p, pl, k, r == rh::rlm::kMixedFiltered, sa, stream, pcm16);
         if (w != RH_OK) return w;
         break;
     default: break;

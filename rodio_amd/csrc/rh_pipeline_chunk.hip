@@ -46,13 +46,23 @@ static_assert(sizeof(ChunkMulti) <= 4096, "the kernarg segment");
 #define RH_CPH_DECL
 #endif
 // C: channels of a frame; KV: KiB of a chunk (8 for stereo: 1024 frames; 4 for mono: 1024 frames too -- the tile stays at 64 runs of 18).
-template <int R, int C, int KV>
+// ST: the sources' sample type.  float: k_rlm_chunk.  int16_t: k_rlm_chunk_pcm16 -- the rows are interleaved 16-bit PCM as they lie in a WAV data
+// chunk; a chunk of P frames is half as many bytes, so the ring's bytes hold FOUR stages of KV * 512 bytes (KV / 2 DMA instructions a lane each:
+// the same bytes in flight), and the lane reads the 8 bytes at k * 512 + lane * 8 of a landed stage for acc[k] -- the four samples whose floats
+// the f32 kernel's lane reads there.  float(s) / 32768 is exact (dasp's i16 -> f32, rh_convert_i16_to_f32), so fma(g, float(s) / 32768, acc) in
+// the sources' order gives the bits of converting first; only the source loop knows the sample type.
+template <int R, int C, int KV, typename ST = float>
 __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs &q, const uint32_t block) {
     typedef Chan<C> CH;
     typedef typename CH::V V;
+    constexpr bool PCM = sizeof(ST) == 2;
     constexpr int NS = 2, H = 4;
     constexpr uint32_t FB = CH::kFB;
     constexpr uint32_t kStage = KV * 1024, P = kStage / FB;   // bytes of a ring stage = one chunk; frames per chunk
+    constexpr int NSI = PCM ? 2 * NS : NS;                    // stages of the ring as the source loop cuts it, of kIn bytes each:
+    constexpr uint32_t kIn = PCM ? kStage / 2 : kStage;       // ... a chunk of the sources' samples
+    constexpr int G = PCM ? KV / 2 : KV;                      // DMA instructions (1 KiB) of a chunk
+    static_assert(KV % 2 == 0 && NSI * kIn == NS * kStage, "the ring's bytes, cut for either sample type");
     constexpr uint32_t MB = NS * kStage + 64;                 // the mixed chunk: halo frames at MB - H * FB .. MB, 16 spare bytes behind it
     __shared__ __attribute__((aligned(1024))) unsigned char smem[MB + kStage + 64];
     lds_u8 *const lds = (lds_u8 *)smem;
@@ -109,29 +119,33 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
     const bool first = (m0 == 0);                              // stream start: x'[-1] = x'[-2] = 0
 
     // ---- the sum of chunk `tile` of every source (k_mix_ring) ----
-    const uint32_t nvec = Ns * C / 4;  // 16-byte vectors of a row (host: whole vectors)
-    const uint32_t v0 = tile * (KV * 64);
-    uint32_t goff[KV];
+    const uint32_t nvec = PCM ? Ns * C / 8 : Ns * C / 4;  // 16-byte vectors of a row (host: whole vectors -- of the sources' samples)
+    const uint32_t v0 = tile * (G * 64);
+    uint32_t goff[G];
 #pragma unroll
-    for (int k = 0; k < KV; ++k) {
+    for (int k = 0; k < G; ++k) {
         uint32_t j = v0 + (uint32_t)k * 64 + lane;
         j = j < nvec ? j : nvec - 1;  // past the end of the row: its last vector again (finite, never a tap of a stored frame)
         goff[k] = j * 16;
     }
     // every chunk but a row's last lies whole inside the row: its DMA instructions are 1 KiB apart in memory as in the LDS and go
     // out as one run (one M0, one offset register: glds16_run)
-    const bool lin = v0 + (uint32_t)(KV * 64) <= nvec;
+    const bool lin = v0 + (uint32_t)(G * 64) <= nvec;
     auto stage_source = [&](uint32_t s_, uint32_t stage) {
         const void *data = (const void *)(uintptr_t)desc[4 * (uint64_t)s_];
         if (lin) {
-            glds16_run<KV>(data, goff[0], lds0 + stage * kStage);
+            glds16_run<G>(data, goff[0], lds0 + stage * kIn);
         } else {
 #pragma unroll
-            for (int k = 0; k < KV; ++k) glds16(data, goff[k], lds0 + stage * kStage + k * 1024);
+            for (int k = 0; k < G; ++k) glds16(data, goff[k], lds0 + stage * kIn + k * 1024);
         }
     };
     if (S) stage_source(0, 0);  // the first two chunks are on their way while the lane works out its taps
     if (S > 1) stage_source(1, 1);
+    if constexpr (PCM) {  // (four stages: the first four)
+        if (S > 2) stage_source(2, 2);
+        if (S > 3) stage_source(3, 3);
+    }
     // the lane's rows of the filter tables and its look-back weight: fetched here, a source loop away from their use
     // Everything the part behind the source loop needs from the kernel arguments is worked out HERE and parked in vector
     // registers: a scalar load of a kernel argument behind the loop is a memory round trip that nothing hides (the compiler
@@ -191,7 +205,7 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
     v4f acc[KV];
 #pragma unroll
     for (int k = 0; k < KV; ++k) acc[k] = v4f{0.f, 0.f, 0.f, 0.f};
-    {
+    if constexpr (!PCM) {
         uint32_t st = 0;
         float g_next = S ? dgain[4] : 0.f;
         for (uint32_t s_ = 0; s_ < S; ++s_) {
@@ -215,6 +229,30 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
                 acc[k].w = fma_(g, v[k].w, acc[k].w);
             }
             st ^= 1u;
+        }
+    } else {
+        uint32_t st = 0;
+        float g_next = S ? dgain[4] : 0.f;
+        for (uint32_t s_ = 0; s_ < S; ++s_) {
+            const float g = g_next;
+            g_next = s_ + 1 < S ? dgain[8 * (uint64_t)(s_ + 1) + 4] : 0.f;
+            // source s_ has landed when at most the groups behind it are outstanding: those of the next three sources, or of what is left of them
+            const uint32_t left = S - 1 - s_;
+            wait_groups<G, NSI>((int)(left < (uint32_t)(NSI - 1) ? left : (uint32_t)(NSI - 1)));
+            const lds_u8 *buf = lds + st * kIn;
+            v4i16 v[KV];
+#pragma unroll
+            for (int k = 0; k < KV; ++k) v[k] = *(const RH_LDS v4i16 *)(buf + k * 512 + lane * 8);  // the samples of acc[k]: 8 bytes
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the chunk is in registers: its stage is free ...
+            if (s_ + NSI < S) stage_source(s_ + NSI, st);        // ... for the source four on, requested before this one is summed
+#pragma unroll
+            for (int k = 0; k < KV; ++k) {
+                acc[k].x = fma_(g, pcm16_f32(v[k].x), acc[k].x);
+                acc[k].y = fma_(g, pcm16_f32(v[k].y), acc[k].y);
+                acc[k].z = fma_(g, pcm16_f32(v[k].z), acc[k].z);
+                acc[k].w = fma_(g, pcm16_f32(v[k].w), acc[k].w);
+            }
+            st = (st + 1u) & (uint32_t)(NSI - 1);
         }
     }
     RH_CPH_DECL
@@ -398,6 +436,12 @@ __device__ __forceinline__ void rlm_chunk_tile(const Params &p, const ChunkArgs 
 template <int R, int C, int KV>
 __global__ __launch_bounds__(64, 2) void k_rlm_chunk(const Params p, const ChunkArgs q) {
     rlm_chunk_tile<R, C, KV>(p, q, blockIdx.x);
+}
+// The same tile over sources that are rows of 16-bit PCM (rh_rlm_set_sources_pcm16): whole 16-byte vectors of int16 on 16-byte boundaries
+// (rh_rlm_pcm16.h decides).  The tiles, the tickets, m_lo and the look-back tables are the f32 plan's.
+template <int R, int C, int KV>
+__global__ __launch_bounds__(64, 2) void k_rlm_chunk_pcm16(const Params p, const ChunkArgs q) {
+    rlm_chunk_tile<R, C, KV, int16_t>(p, q, blockIdx.x);
 }
 // Several batches in ONE launch (the filter classes of a mixer, rh_rlm_set_filters): workgroups first[k] .. first[k+1]-1 are class k's launch of
 // k_rlm_chunk, with that class's arguments -- its own sources, tables, hand-off words, ticket counters and output row.  Nothing crosses
@@ -905,14 +949,15 @@ struct ChunkInst {
     uint32_t C;
     int R, KV;
     const void *one, *multi, *classes;  // (nullptr: no such instance)
+    const void *pcm16 = nullptr;        // k_rlm_chunk_pcm16
 };
 #define RH_FN(k) reinterpret_cast<const void *>(&k)
 static const ChunkInst kChunk[] = {
-    {2, 9, 4, RH_FN((k_rlm_chunk<9, 2, 4>)), RH_FN((k_rlm_chunk_multi<9, 2, 4>)), nullptr},
-    {2, 18, 8, RH_FN((k_rlm_chunk<18, 2, 8>)), RH_FN((k_rlm_chunk_multi<18, 2, 8>)), RH_FN((k_rlm_chunk_classes<18, 2, 8>))},
-    {2, 18, 4, RH_FN((k_rlm_chunk<18, 2, 4>)), RH_FN((k_rlm_chunk_multi<18, 2, 4>)), RH_FN((k_rlm_chunk_classes<18, 2, 4>))},
-    {1, 18, 4, RH_FN((k_rlm_chunk<18, 1, 4>)), RH_FN((k_rlm_chunk_multi<18, 1, 4>)), RH_FN((k_rlm_chunk_classes<18, 1, 4>))},
-    {1, 18, 2, RH_FN((k_rlm_chunk<18, 1, 2>)), RH_FN((k_rlm_chunk_multi<18, 1, 2>)), RH_FN((k_rlm_chunk_classes<18, 1, 2>))},
+    {2, 9, 4, RH_FN((k_rlm_chunk<9, 2, 4>)), RH_FN((k_rlm_chunk_multi<9, 2, 4>)), nullptr},  // (RH_CHUNK_HALF, a tuning aid: PCM16 rows take the converted copy there)
+    {2, 18, 8, RH_FN((k_rlm_chunk<18, 2, 8>)), RH_FN((k_rlm_chunk_multi<18, 2, 8>)), RH_FN((k_rlm_chunk_classes<18, 2, 8>)), RH_FN((k_rlm_chunk_pcm16<18, 2, 8>))},
+    {2, 18, 4, RH_FN((k_rlm_chunk<18, 2, 4>)), RH_FN((k_rlm_chunk_multi<18, 2, 4>)), RH_FN((k_rlm_chunk_classes<18, 2, 4>)), RH_FN((k_rlm_chunk_pcm16<18, 2, 4>))},
+    {1, 18, 4, RH_FN((k_rlm_chunk<18, 1, 4>)), RH_FN((k_rlm_chunk_multi<18, 1, 4>)), RH_FN((k_rlm_chunk_classes<18, 1, 4>)), RH_FN((k_rlm_chunk_pcm16<18, 1, 4>))},
+    {1, 18, 2, RH_FN((k_rlm_chunk<18, 1, 2>)), RH_FN((k_rlm_chunk_multi<18, 1, 2>)), RH_FN((k_rlm_chunk_classes<18, 1, 2>)), RH_FN((k_rlm_chunk_pcm16<18, 1, 2>))},
 };
 #undef RH_FN
 static const ChunkInst *chunk_inst(int R, uint32_t channels, int KV) {
@@ -923,6 +968,10 @@ static const ChunkInst *chunk_inst(int R, uint32_t channels, int KV) {
 const void *chunk_kernel(int R, uint32_t channels, int KV) {
     const ChunkInst *c = chunk_inst(R, channels, KV);
     return c ? c->one : nullptr;
+}
+const void *chunk_kernel_pcm16(int R, uint32_t channels, int KV) {
+    const ChunkInst *c = chunk_inst(R, channels, KV);
+    return c ? c->pcm16 : nullptr;
 }
 
 // The arguments of k_rlm_chunk for the batch that is set: the chunk plan's tables in place of the active plan's
@@ -1008,12 +1057,16 @@ extern "C" int rh_debug_cls_stamps(unsigned long long *dst, size_t n) {
 #endif
 
 // Mix first in one kernel: every tile sums its aligned chunk of every source, then converts and filters its part of the mix
-rh_status launch_chunk(rh_rlm *p, Params &k, hipStream_t s) {
+rh_status launch_chunk(rh_rlm *p, Params &k, hipStream_t s, bool pcm16) {
     ChunkArgs ca;
     chunk_params(p, k, ca);
+    if (pcm16) {  // the int16 rows themselves: their table, the instance that reads them, and its own residency
+        k.srcs = p->d_pcm;
+        k.direct = (p->chunk.direct_pcm && p->exclusive) ? 1u : 0u;
+    }
     const uint32_t grid = k.direct ? k.n_tiles : rh::rlm::sharded_grid(k.n_tiles);  // by ticket: whole rounds of the eight counters (k_rlm_chunk)
     void *args[] = {&k, &ca};
-    const hipError_t e = hipLaunchKernel(p->chunk.fn, dim3(grid), dim3(64), args, 0, s);
+    const hipError_t e = hipLaunchKernel(pcm16 ? p->chunk.fn_pcm : p->chunk.fn, dim3(grid), dim3(64), args, 0, s);
     if (e != hipSuccess) {
         rh::set_hip_error(e, "k_rlm_chunk launch");
         return RH_ERR_HIP;

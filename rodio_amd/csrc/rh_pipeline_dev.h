@@ -72,6 +72,10 @@ typedef RH_LDS v2u64 lds_u64x2;
 #define RH_GLB __attribute__((address_space(1)))
 typedef RH_GLB const float glb_cf32;  // a pointer loaded from a descriptor is generic: say it is global,
 typedef RH_GLB const v2f glb_cf2;     // or every source load is a flat_load that also blocks lgkmcnt
+// Sources set as 16-bit PCM (k_rlm_chunk_pcm16, k_mix_rows_pcm16): four samples are 8 bytes; dasp's i16 -> f32 is `s as f32 / 32768.0`, and a
+// division by a power of two is the multiplication by its inverse, exact for every int16
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float pcm16_f32(short s) { return (float)s * 0x1p-15f; }
 
 // ---- hand-counted memory pipeline -------------------------------------------------------------
 // One LDS-DMA instruction: 64 lanes x 16 bytes from base + voff (per lane) land at LDS byte

@@ -17,6 +17,7 @@
 
 #include "rh_common.h"
 #include "rh_rlm_launch.h"  // the launch decisions: route, row_cut, Tickets, sblk_geom
+#include "rh_rlm_pcm16.h"   // ... and, for sources set as 16-bit PCM: the rows themselves or a converted copy
 
 namespace rh {
 struct ResampleGeom {
@@ -196,6 +197,9 @@ inline int kv_needed(uint64_t L, uint32_t F, uint32_t T, uint32_t channels) {
 struct ChunkPlan {
     int R = 18, KV = 8;                // frames per lane; KiB per chunk (stereo: 18 / 8; mono: 18 / 4: 1024 frames per chunk either way)
     const void *fn = nullptr;          // the instance for (R, channels, KV)
+    const void *fn_pcm = nullptr;      // ... and the one that reads rows of 16-bit PCM (k_rlm_chunk_pcm16; nullptr: none)
+    int resident_pcm = 0;
+    bool direct_pcm = false;           // `direct` by that instance's own residency
     int tabs_R = 0;                    // the R the filter tables were built for (0: none yet)
     bool ok = false;                   // the batch that is set can take the kernel
     Uniforms uni;
@@ -285,6 +289,24 @@ struct rh_rlm {
     hipEvent_t h_ring_ev[kDescRing] = {nullptr, nullptr, nullptr, nullptr};
     int h_ring_next = 0;
     std::vector<float> gains;     // per-source Amplify factors (1.0 when unset)
+    // Sources set as 16-bit PCM (rh_rlm_set_sources_pcm16).  The int16 rows have a descriptor table of their own (h_pcm / d_pcm: SrcDesc::data
+    // holds the int16 pointer), which the native kernels read; h_desc / d_srcs are the f32 view -- they receive the rows of the converted copy
+    // when the first run that needs it makes it (pcm_f32_ready), once per set_sources.  The stream entries upload their own rows into d_srcs
+    // and know nothing of all this.
+    bool pcm = false;
+    std::vector<SrcDesc> h_pcm;
+    SrcDesc *d_pcm = nullptr;
+    uint64_t pcm_bits = 0;             // the OR of the rows' addresses (rh::rlm::Pcm16In::addr_bits)
+    float *d_pcm_f32 = nullptr;        // the converted copy, row s at pcm_off[s] floats (every row on a 256-byte boundary)
+    std::vector<size_t> pcm_off;
+    bool pcm_converted = false;        // the conversion is queued (on pcm_stream, pcm_ev behind it)
+    uint64_t pcm_table_version = ~0ull;  // srcs_version right after d_srcs received the copy's rows
+    hipStream_t pcm_stream = nullptr;
+    hipEvent_t pcm_ev = nullptr;
+    int32_t last_native = 0;           // rh_rlm_source_format: the last one-shot run read the int16 rows themselves
+    uint32_t pcm_n = 0, pcm_eq = 0;    // n_sources / eq_frames / out_frames as set_sources_pcm16 left them: a stream that ran on the handle since has
+    uint64_t pcm_out = 0;              // put its own block there, and a one-shot run must not read the int16 rows by those (pcm_current)
+    bool pcm_current() const { return pcm_n == n_sources && pcm_eq == eq_frames && pcm_out == out_frames && h_pcm.size() == n_sources; }
     // block streaming with per-source states (rh_rlm_stream_block_v)
     std::vector<uint64_t> st_total;  // input frames of a source that has ended (~0: still live)
     uint32_t st_cols = 0;            // columns of an aggregate row for the stream (0: no such stream yet)
@@ -354,8 +376,9 @@ enum TabKind { kTabFast, kTabWave, kTabRag };
 VariantTab variant_tab(TabKind kind, bool mono);             // the instances of k_rlm_fast / k_rlm_wave / k_rlm_fast<RAG> + k_rlm_resid
 // rh_pipeline_chunk.hip
 const void *chunk_kernel(int R, uint32_t channels, int KV);  // the instance of k_rlm_chunk, or nullptr
-// k_rlm_chunk for the batch that is set, `k` being the launch_params of the run
-rh_status launch_chunk(rh_rlm *p, Params &k, hipStream_t s);
+const void *chunk_kernel_pcm16(int R, uint32_t channels, int KV);  // ... of k_rlm_chunk_pcm16
+// k_rlm_chunk for the batch that is set, `k` being the launch_params of the run (pcm16: k_rlm_chunk_pcm16 over the int16 rows)
+rh_status launch_chunk(rh_rlm *p, Params &k, hipStream_t s, bool pcm16 = false);
 // The classes of a mixer with per-source filters as ONE launch of k_rlm_chunk_multi (class k's mix into rows[k]): *taken = false and nothing
 // done when a class does not take the k_rlm_chunk path, the classes' instances differ, or there are more than fit one kernarg segment
 // (*summed: the launch added the classes' mixes itself, into dst_sum -- k_rlm_chunk_classes; the rows are then unwritten)
@@ -363,7 +386,9 @@ rh_status chunk_launch_classes(rh_rlm *const *classes, float *const *rows, uint6
 // rh_pipeline_mix.hip
 // Mix first: sums the sources of `k` at the input rate (k_mix_rows / k_mix_ring; pre: then filters the sum there) and turns `k` into the fused
 // launch over that one stream
-rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const StreamArgs &sa, rh_stream stream);
+// (pcm16: k_mix_rows_pcm16 over the int16 rows; mixed_row_cut: the cut that launch will make)
+rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const StreamArgs &sa, rh_stream stream, bool pcm16 = false);
+rh::rlm::RowCut mixed_row_cut(const rh_rlm *p, uint32_t count, bool pre, const StreamArgs &sa);
 // k_rlm_state on `s`: folds a block's aggregates into column 0 of the per-source rows (see rh_pipeline_stream.hip)
 void launch_state(hipStream_t s, unsigned long long *gran, const Tables *tabs, uint32_t n_sources, uint32_t cols, uint32_t last_col, uint32_t J, uint32_t epoch, uint32_t next_epoch);
 // k_rlm_state_sum on `s`: the sum of the live sources' states (column 0 of their rows, tagged `tag`) -> the 4 words of a summed state
@@ -408,4 +433,7 @@ rh_status build_chunk(rh_rlm *p);
 bool pair_ok(rh_rlm *p, const Plan &pl);
 rh_status activate_plan(rh_rlm *p, Plan *pl);
 rh_status upload_descriptors(rh_rlm *p, uint32_t n, hipStream_t s);
+// Sources set as 16-bit PCM: the converted copy is made (once per set_sources, on `s`), ordered in front of what `s` runs next, and d_srcs
+// holds its rows.  RH_ERR_NOMEM: no memory for the copy.
+rh_status pcm_f32_ready(rh_rlm *p, hipStream_t s);
 }  // namespace rhp

@@ -143,6 +143,147 @@ __global__ __launch_bounds__(256) void k_mix_rows(const SrcDesc *__restrict__ sr
     }
 }
 
+// k_mix_rows over rows of 16-bit PCM (rh_rlm_set_sources_pcm16; SrcDesc::data holds the int16 row, n_floats counts samples): the same cut, groups,
+// partial rows and guarded last workgroup, written out a second time so that k_mix_rows compiles to what it always did.  A lane's vector is the
+// 8 bytes of the four samples the f32 kernel's lane reads as 16: rows on 8-byte boundaries, of any length (the samples behind the last four go
+// one by one, as the floats do there); no load reaches past sample n_floats - 1.  float(s) / 32768 is exact (dasp's i16 -> f32), so the sum has
+// the bits of converting first.
+struct MixPcm16 {
+    typedef RH_GLB const v4i16 GV;  // the four samples of an accumulator
+    typedef v4i16 V;
+    typedef RH_GLB const short GS;
+    static __device__ __forceinline__ v4f f(V v) { return v4f{pcm16_f32(v.x), pcm16_f32(v.y), pcm16_f32(v.z), pcm16_f32(v.w)}; }
+    static __device__ __forceinline__ float f1(short s) { return pcm16_f32(s); }
+};
+template <int U>
+__global__ __launch_bounds__(256) void k_mix_rows_pcm16(const SrcDesc *__restrict__ srcs_all, const uint32_t n_sources_all, float *__restrict__ y_all, const uint64_t n_floats, SrcDesc *__restrict__ ydesc_all,
+                                                        const uint32_t frames, const uint32_t out_frames, const float *desc_row_all, const uint64_t group_stride) {
+    typedef MixPcm16 IN;
+    typedef IN::V VIN;
+    typedef __attribute__((address_space(4))) const uint64_t cu64;
+    typedef __attribute__((address_space(4))) const float cf32;
+    typedef IN::GV glb_cf4;  // (the four samples of an accumulator)
+    const uint32_t per_group = (n_sources_all + gridDim.y - 1) / gridDim.y, s_first = blockIdx.y * per_group;
+    const uint32_t n_sources = s_first < n_sources_all ? (n_sources_all - s_first < per_group ? n_sources_all - s_first : per_group) : 0u;
+    const SrcDesc *const srcs = srcs_all + s_first;
+    float *const y = y_all + (uint64_t)blockIdx.y * group_stride;
+    SrcDesc *const ydesc = ydesc_all + blockIdx.y;
+    const float *const desc_row = desc_row_all + (uint64_t)blockIdx.y * group_stride;
+    cu64 *const desc = (cu64 *)(uintptr_t)srcs;
+    cf32 *const dgain = (cf32 *)(uintptr_t)srcs;
+    const uint64_t nvec = n_floats / 4;
+    const uint64_t base = (uint64_t)blockIdx.x * (256u * U) + threadIdx.x;
+    v4f acc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] = v4f{0.f, 0.f, 0.f, 0.f};
+    // sources per step: 8 / U as there, and twice that where the scalar registers hold the pointers and gains of two such steps (U >= 2): half the
+    // bytes a load, the same bytes in flight in the same vector registers
+    constexpr int SB = U == 1 ? 8 : 2 * (8 / U > 2 ? 8 / U : 2);
+    if (base + (uint64_t)(U - 1) * 256u < nvec) {  // every vector of this lane is whole and inside
+        // Two register sets: while the vectors of one step are summed, the loads of the next are in flight and the pointers
+        // and gains of the step after that are on their way through the scalar cache (the body is written out twice so that
+        // the sets swap without moves).
+        const uint32_t steps = n_sources / SB;
+        uint64_t pN[SB];
+        float gN[SB];
+        auto fetch_desc = [&](uint32_t j) {
+#pragma unroll
+            for (int k = 0; k < SB; ++k) {
+                pN[k] = desc[4 * (uint64_t)(j * SB + k)];
+                gN[k] = dgain[8 * (uint64_t)(j * SB + k) + 4];
+            }
+        };
+        auto issue = [&](VIN (&v)[SB][U], float (&g)[SB]) {
+#pragma unroll
+            for (int k = 0; k < SB; ++k) {
+                glb_cf4 *const ptr = (glb_cf4 *)(uintptr_t)pN[k];
+                g[k] = gN[k];
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[k][u] = __builtin_nontemporal_load(ptr + base + (uint64_t)u * 256u);
+            }
+        };
+        auto consume = [&](const VIN (&v)[SB][U], const float (&g)[SB]) {
+#pragma unroll
+            for (int k = 0; k < SB; ++k)
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const v4f x = IN::f(v[k][u]);
+                    acc[u].x = fma_(g[k], x.x, acc[u].x);
+                    acc[u].y = fma_(g[k], x.y, acc[u].y);
+                    acc[u].z = fma_(g[k], x.z, acc[u].z);
+                    acc[u].w = fma_(g[k], x.w, acc[u].w);
+                }
+        };
+        VIN vA[SB][U], vB[SB][U];
+        float gA[SB], gB[SB];
+        // (the loads of the next step are issued unconditionally inside the loop: a conditional issue makes the compiler wait
+        // for the newest load of either path, which drains the pipeline every step)
+        if (steps) {
+            fetch_desc(0);
+            issue(vA, gA);
+            if (steps > 1) fetch_desc(1);
+            uint32_t j = 0;
+            for (; j + 2 < steps; j += 2) {
+                issue(vB, gB);         // step j+1
+                fetch_desc(j + 2);
+                consume(vA, gA);       // step j
+                issue(vA, gA);         // step j+2
+                fetch_desc(j + 3 < steps ? j + 3 : steps - 1);
+                consume(vB, gB);       // step j+1
+            }
+            if (j + 1 < steps) {  // two steps left: A in flight, B's descriptors fetched
+                issue(vB, gB);
+                consume(vA, gA);
+                consume(vB, gB);
+            } else {
+                consume(vA, gA);
+            }
+        }
+        for (uint32_t s = steps * SB; s < n_sources; ++s) {
+            glb_cf4 *const ptr = (glb_cf4 *)(uintptr_t)(desc[4 * (uint64_t)s]);
+            const float g = dgain[8 * (uint64_t)s + 4];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const v4f v = IN::f(__builtin_nontemporal_load(ptr + base + (uint64_t)u * 256u));
+                acc[u].x = fma_(g, v.x, acc[u].x);
+                acc[u].y = fma_(g, v.y, acc[u].y);
+                acc[u].z = fma_(g, v.z, acc[u].z);
+                acc[u].w = fma_(g, v.w, acc[u].w);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) *reinterpret_cast<v4f *>(y + 4 * (base + (uint64_t)u * 256u)) = acc[u];
+    } else {  // the last workgroup: vector by vector, guarded
+        for (int u = 0; u < U; ++u) {
+            const uint64_t i = base + (uint64_t)u * 256u;
+            if (i >= nvec) break;
+            v4f a = v4f{0.f, 0.f, 0.f, 0.f};
+            for (uint32_t s = 0; s < n_sources; ++s) {
+                glb_cf4 *const ptr = (glb_cf4 *)(uintptr_t)(desc[4 * (uint64_t)s]);
+                const float g = dgain[8 * (uint64_t)s + 4];
+                const v4f v = IN::f(ptr[i]);
+                a.x = fma_(g, v.x, a.x), a.y = fma_(g, v.y, a.y), a.z = fma_(g, v.z, a.z), a.w = fma_(g, v.w, a.w);
+            }
+            *reinterpret_cast<v4f *>(y + 4 * i) = a;
+        }
+    }
+    if (blockIdx.x == 0) {
+        const uint64_t t = nvec * 4 + threadIdx.x;  // the floats behind the last whole vector (a mono batch of a length not divisible by 4)
+        if (t < n_floats) {
+            float a = 0.f;
+            for (uint32_t s = 0; s < n_sources; ++s) a = fma_(dgain[8 * (uint64_t)s + 4], IN::f1(((IN::GS *)(uintptr_t)(desc[4 * (uint64_t)s]))[t]), a);
+            y[t] = a;
+        }
+        if (threadIdx.x == 0) {  // the one-entry descriptor table the fused launch behind this one reads
+            ydesc->data = desc_row;  // the row the launch behind this one reads: the mix, or what a filter makes of it
+            ydesc->frames = frames;
+            ydesc->out_frames = out_frames;
+            ydesc->gain = 1.0f;
+            ydesc->pad[0] = ydesc->pad[1] = ydesc->pad[2] = 0;
+        }
+    }
+}
+
 // The same sum for long rows, in the shape that reaches the read ceiling of this part (tools/ubench/stream_ring: 7.19 TB/s):
 // one wave owns chunk t -- 8 KiB, aligned -- of EVERY source; it pulls the chunks through a ring of NS LDS stages with LDS-DMA
 // (8 instructions of 1 KiB per source, no registers held by data in flight), reads its own 8 vectors of a landed stage back
@@ -290,13 +431,19 @@ namespace rhp {
 // Mix first: a filtered batch of equal-length sources -- or a block of a stream on the summed state -- is summed at the input rate
 // (k_mix_rows / k_mix_ring: the one pass over the input; filter_first: then filtered there), and `k` becomes the fused launch that converts
 // and filters that ONE stream
-rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const StreamArgs &sa, rh_stream stream) {
+rh::rlm::RowCut mixed_row_cut(const rh_rlm *p, uint32_t count, bool pre, const StreamArgs &sa) {
+    const uint64_t n_floats = (uint64_t)p->eq_frames * p->cfg.channels;
+    const char *ku = rh::knob(rh::K_MIX_U), *kg = rh::knob(rh::K_MIX_GROUPS);
+    return rh::rlm::row_cut({n_floats, count, (uint32_t)rh::g_num_cus, pre, sa.mode != 0, (uint64_t)p->cfg.max_in_frames * p->cfg.channels, ku ? atoi(ku) : rh::rlm::kUnset,
+                             kg ? atoi(kg) : rh::rlm::kUnset});
+}
+
+rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const StreamArgs &sa, rh_stream stream, bool pcm16) {
     hipStream_t s = rh::as_stream(stream);
     const uint32_t count = k.n_sources;
     const uint64_t n_floats = (uint64_t)p->eq_frames * p->cfg.channels;
-    const char *ku = rh::knob(rh::K_MIX_U), *kg = rh::knob(rh::K_MIX_GROUPS);
-    const rh::rlm::RowCut c = rh::rlm::row_cut({n_floats, count, (uint32_t)rh::g_num_cus, pre, sa.mode != 0, (uint64_t)p->cfg.max_in_frames * p->cfg.channels,
-                                                ku ? atoi(ku) : rh::rlm::kUnset, kg ? atoi(kg) : rh::rlm::kUnset});
+    const rh::rlm::RowCut c = mixed_row_cut(p, count, pre, sa);
+    if (pcm16 && (c.ring || pre || sa.mode)) return RH_ERR_UNSUPPORTED;  // (rh_rlm_pcm16.h sends only k_mix_rows' one-shot runs here)
     if (c.need > p->mix_floats) {
         const rh_status w = wait_idle(p);
         if (w != RH_OK) return w;
@@ -308,7 +455,11 @@ rh_status launch_mixed(rh_rlm *p, const Plan &pl, Params &k, bool pre, const Str
     SrcDesc *const ydesc = reinterpret_cast<SrcDesc *>(p->d_mix + rh::rlm::row_cut_desc_offset(p->mix_floats));
     float *const frow = pre ? p->d_mix + c.row : p->d_mix;  // the row the fused launch reads
     const uint32_t nf = p->eq_frames, mf = (uint32_t)p->out_frames;
-    if (c.ring >= 3) hipLaunchKernelGGL(k_mix_ring<3>, dim3((uint32_t)c.ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
+    if (pcm16) {  // the int16 rows themselves, through their own table
+        if (c.U == 1) hipLaunchKernelGGL(k_mix_rows_pcm16<1>, dim3(c.wgs, c.groups), dim3(256), 0, s, p->d_pcm, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row);
+        else if (c.U == 2) hipLaunchKernelGGL(k_mix_rows_pcm16<2>, dim3(c.wgs, c.groups), dim3(256), 0, s, p->d_pcm, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row);
+        else hipLaunchKernelGGL(k_mix_rows_pcm16<4>, dim3(c.wgs, c.groups), dim3(256), 0, s, p->d_pcm, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row);
+    } else if (c.ring >= 3) hipLaunchKernelGGL(k_mix_ring<3>, dim3((uint32_t)c.ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
     else if (c.ring == 2) hipLaunchKernelGGL(k_mix_ring<2>, dim3((uint32_t)c.ring_waves), dim3(64), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, sa.src_off);
     else if (c.U == 1) hipLaunchKernelGGL(k_mix_rows<1>, dim3(c.wgs, c.groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row, sa.src_off);
     else if (c.U == 2) hipLaunchKernelGGL(k_mix_rows<2>, dim3(c.wgs, c.groups), dim3(256), 0, s, k.srcs, count, p->d_mix, n_floats, ydesc, nf, mf, frow, (uint64_t)c.row, sa.src_off);

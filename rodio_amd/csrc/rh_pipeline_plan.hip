@@ -291,9 +291,14 @@ rh_status build_chunk(rh_rlm *p) {
         c.fn = fn;
         c.R = R;
         c.KV = KV;
+        // the instance over rows of 16-bit PCM, with its own residency (a handle whose sources are f32 never launches it)
+        c.fn_pcm = chunk_kernel_pcm16(R, C, KV);
+        c.resident_pcm = 0;
+        if (c.fn_pcm && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.resident_pcm, c.fn_pcm, 64, 0) != hipSuccess || c.resident_pcm < 1)) c.fn_pcm = nullptr;
     }
     if (c.resident_per_cu < 1) return RH_OK;
     c.direct = tiles <= (uint64_t)rh::g_num_cus * (uint64_t)c.resident_per_cu;  // every tile resident at once: no tickets
+    c.direct_pcm = c.fn_pcm && tiles <= (uint64_t)rh::g_num_cus * (uint64_t)c.resident_pcm;
     const M2 A{-(double)p->coeffs[3], -(double)p->coeffs[4], 1.0, 0.0};
     M2 Tm, Ti;
     scan_basis((double)p->coeffs[3], (double)p->coeffs[4], Tm, Ti);
@@ -477,6 +482,83 @@ rh_status upload_descriptors(rh_rlm *p, uint32_t n, hipStream_t s) {
     return RH_OK;
 }
 
+// ---- sources set as 16-bit PCM: the converted copy ----
+// The copy goes (with the sources that were set: rh_rlm_set_sources*, rh_rlm_destroy).  Nothing of the handle may still read it.
+static rh_status pcm_release(rh_rlm *p) {
+    if (p->d_pcm_f32) {
+        const rh_status w = wait_idle(p);
+        if (p->pcm_converted && p->pcm_ev) (void)hipEventSynchronize(p->pcm_ev);  // (a conversion whose run never followed)
+        if (w != RH_OK) return w;
+        RH_HIP_TRY(hipFree(p->d_pcm_f32));
+        p->d_pcm_f32 = nullptr;
+    }
+    p->pcm = false;
+    p->pcm_converted = false;
+    p->pcm_table_version = ~0ull;
+    p->pcm_off.clear();
+    p->pcm_bits = 0;
+    p->last_native = 0;
+    return RH_OK;
+}
+// Room for the copy: row s at pcm_off[s], every row on a 256-byte boundary with a line to spare behind it; rows[s] = where it will lie
+static rh_status pcm_alloc(rh_rlm *p, std::vector<const float *> *rows) {
+    const size_t n = p->h_pcm.size();
+    if (!p->d_pcm_f32) {
+        p->pcm_off.assign(n, 0);
+        size_t total = 0;
+        for (size_t s = 0; s < n; ++s) {
+            p->pcm_off[s] = total;
+            total += (((size_t)p->h_pcm[s].frames * p->cfg.channels + 63) & ~(size_t)63) + 64;
+        }
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->d_pcm_f32), std::max<size_t>(total, 64) * sizeof(float));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            p->d_pcm_f32 = nullptr;
+            rh::set_hip_error(e, "the f32 copy of PCM16 sources");
+            return e == hipErrorOutOfMemory ? RH_ERR_NOMEM : RH_ERR_HIP;
+        }
+    }
+    rows->resize(n);
+    for (size_t s = 0; s < n; ++s) (*rows)[s] = p->h_pcm[s].frames ? p->d_pcm_f32 + p->pcm_off[s] : nullptr;
+    return RH_OK;
+}
+// rh_convert_i16_to_f32 of every row into the copy, on `s`, once; a later run on another stream waits for it there
+static rh_status pcm_convert(rh_rlm *p, hipStream_t s) {
+    if (!p->pcm_converted) {
+        for (size_t k = 0; k < p->h_pcm.size(); ++k) {
+            const size_t ns = (size_t)p->h_pcm[k].frames * p->cfg.channels;
+            if (!ns) continue;
+            const rh_status st = rh_convert_i16_to_f32(p->d_pcm_f32 + p->pcm_off[k], reinterpret_cast<const int16_t *>(p->h_pcm[k].data), ns, reinterpret_cast<rh_stream>(s));
+            if (st != RH_OK) return st;
+        }
+        if (!p->pcm_ev) RH_HIP_TRY(hipEventCreateWithFlags(&p->pcm_ev, hipEventDisableTiming));
+        RH_HIP_TRY(hipEventRecord(p->pcm_ev, s));
+        p->pcm_stream = s;
+        p->pcm_converted = true;
+    } else if (s != p->pcm_stream) {
+        RH_HIP_TRY(hipStreamWaitEvent(s, p->pcm_ev, 0));
+    }
+    return RH_OK;
+}
+rh_status pcm_f32_ready(rh_rlm *p, hipStream_t s) {
+    if (!p->pcm) return RH_OK;
+    if (p->pcm_table_version != p->srcs_version) {  // d_srcs does not hold the copy's rows (yet, or any more: a stream's blocks, new gains)
+        std::vector<const float *> rows;
+        rh_status st = pcm_alloc(p, &rows);
+        if (st == RH_OK) st = wait_idle(p);
+        if (st != RH_OK) return st;
+        if (p->h_desc.size() != p->h_pcm.size()) return RH_ERR_INVALID;  // (a stream has taken the handle's table over: set the sources again)
+        for (size_t k = 0; k < rows.size(); ++k) {
+            p->h_desc[k] = p->h_pcm[k];
+            p->h_desc[k].data = rows[k];
+        }
+        if (!rows.empty()) RH_HIP_TRY(hipMemcpy(p->d_srcs, p->h_desc.data(), sizeof(SrcDesc) * rows.size(), hipMemcpyHostToDevice));
+        p->srcs_version += 1;
+        p->pcm_table_version = p->srcs_version;
+    }
+    return pcm_convert(p, s);
+}
+
 }  // namespace rhp
 
 namespace rh {
@@ -644,6 +726,9 @@ rh_status rh_rlm_destroy(rh_rlm *p) {
     if (p->d_gran) (void)hipFree(p->d_gran);
     if (p->d_ctl) (void)hipFree(p->d_ctl);
     if (p->d_mix) (void)hipFree(p->d_mix);
+    if (p->d_pcm_f32) (void)hipFree(p->d_pcm_f32);
+    if (p->d_pcm) (void)hipFree(p->d_pcm);
+    if (p->pcm_ev) (void)hipEventDestroy(p->pcm_ev);
     if (p->chunk.d_tabs) (void)hipFree(p->chunk.d_tabs);
     if (p->chunk.d_pow) (void)hipFree(p->chunk.d_pow);
     if (p->chunk.d_uni) (void)hipFree(p->chunk.d_uni);
@@ -665,9 +750,12 @@ rh_status rh_rlm_destroy(rh_rlm *p) {
 
 // on_stream != nullptr: the table travels on that stream through the page-locked ring (ordered behind the launches already
 // queued there, no host synchronisation) -- what rh_biquad mode 1 does per call; nullptr: the synchronous form of the C ABI.
-static rh_status set_sources_impl(rh_rlm *p, const float *const *srcs_host, const uint64_t *in_frames_host, uint32_t n_sources, const hipStream_t *on_stream) {
+// pcm_host != nullptr (and srcs_host == nullptr): the rows are 16-bit PCM -- any 2-byte boundary; the f32 table keeps null rows until a run needs the
+// converted copy (pcm_f32_ready), the int16 rows go into a table of their own.
+static rh_status set_sources_impl(rh_rlm *p, const float *const *srcs_host, const uint64_t *in_frames_host, uint32_t n_sources, const hipStream_t *on_stream,
+                                  const int16_t *const *pcm_host = nullptr) {
     RH_REQUIRE_INIT();
-    if (!p || (n_sources && (!srcs_host || !in_frames_host))) return RH_ERR_INVALID;
+    if (!p || (n_sources && ((!srcs_host && !pcm_host) || !in_frames_host))) return RH_ERR_INVALID;
     if (n_sources > p->cfg.max_sources) return RH_ERR_CAPACITY;
     std::vector<SrcDesc> &h = p->h_desc;
     h.resize(n_sources);
@@ -675,12 +763,16 @@ static rh_status set_sources_impl(rh_rlm *p, const float *const *srcs_host, cons
     bool equal = true;
     for (uint32_t s = 0; s < n_sources; ++s) {
         if (in_frames_host[s] > p->cfg.max_in_frames) return RH_ERR_CAPACITY;
-        if (in_frames_host[s] && (!srcs_host[s] || (reinterpret_cast<uintptr_t>(srcs_host[s]) & 15u))) return RH_ERR_INVALID;
+        if (pcm_host) {
+            if (in_frames_host[s] && (!pcm_host[s] || (reinterpret_cast<uintptr_t>(pcm_host[s]) & 1u))) return RH_ERR_INVALID;
+        } else if (in_frames_host[s] && (!srcs_host[s] || (reinterpret_cast<uintptr_t>(srcs_host[s]) & 15u))) {
+            return RH_ERR_INVALID;
+        }
         rh::ResampleGeom g;
         rh_status st = rh::make_resample_geom(in_frames_host[s], p->cfg.from_rate, p->cfg.to_rate, p->cfg.channels, p->cfg.span_len, &g);
         if (st != RH_OK) return st;
         if (g.out_frames >= (1ull << 31)) return RH_ERR_UNSUPPORTED;  // 32-bit frame indices in the kernels
-        h[s] = SrcDesc{srcs_host[s], (uint32_t)in_frames_host[s], (uint32_t)g.out_frames, s < p->gains.size() ? p->gains[s] : 1.0f, {0, 0, 0}};
+        h[s] = SrcDesc{pcm_host ? nullptr : srcs_host[s], (uint32_t)in_frames_host[s], (uint32_t)g.out_frames, s < p->gains.size() ? p->gains[s] : 1.0f, {0, 0, 0}};
         if (g.out_frames > M) M = g.out_frames;
         equal = equal && in_frames_host[s] == in_frames_host[0];
     }
@@ -694,12 +786,24 @@ static rh_status set_sources_impl(rh_rlm *p, const float *const *srcs_host, cons
         if (w != RH_OK) return w;
         if (n_sources) RH_HIP_TRY(hipMemcpy(p->d_srcs, h.data(), sizeof(SrcDesc) * n_sources, hipMemcpyHostToDevice));
         p->srcs_version += 1;
+        if (pcm_host) {
+            p->h_pcm = h;
+            p->pcm_bits = 0;
+            for (uint32_t s = 0; s < n_sources; ++s) {
+                p->h_pcm[s].data = reinterpret_cast<const float *>(pcm_host[s]);  // (the kernels that take this table read int16 there)
+                if (in_frames_host[s]) p->pcm_bits |= (uint64_t)reinterpret_cast<uintptr_t>(pcm_host[s]);
+            }
+            if (!p->d_pcm) RH_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p->d_pcm), sizeof(SrcDesc) * p->cfg.max_sources));
+            if (n_sources) RH_HIP_TRY(hipMemcpy(p->d_pcm, p->h_pcm.data(), sizeof(SrcDesc) * n_sources, hipMemcpyHostToDevice));
+            p->pcm = true;
+        }
     }
     p->equal = equal;
     p->eq_frames = n_sources ? (uint32_t)in_frames_host[0] : 0;
     p->n_sources = n_sources;
     p->out_frames = M;
     p->chunk.ok = false;
+    p->pcm_n = p->n_sources, p->pcm_eq = p->eq_frames, p->pcm_out = p->out_frames;
     // equal-length batch: the merged-state kernel; otherwise the general one
     if (equal && !p->cfg.force_general) {
         const rh_status st = activate_plan(p, &p->fast);
@@ -761,17 +865,59 @@ static rh_status set_sources_classes(rh_rlm *p, const float *const *srcs_host, c
     return RH_OK;
 }
 
-rh_status rh_rlm_set_sources(rh_rlm *p, const float *const *srcs_host, const uint64_t *in_frames_host, uint32_t n_sources) {
+static rh_status set_sources_any(rh_rlm *p, const float *const *srcs_host, const int16_t *const *pcm_host, const uint64_t *in_frames_host, uint32_t n_sources) {
+    RH_REQUIRE_INIT();
+    if (p) {  // either entry replaces what the other set
+        const rh_status r = pcm_release(p);
+        if (r != RH_OK) return r;
+    }
     if (p && !p->filters.empty()) {
-        RH_REQUIRE_INIT();
-        return set_sources_classes(p, srcs_host, in_frames_host, n_sources);
+        if (!pcm_host) return set_sources_classes(p, srcs_host, in_frames_host, n_sources);
+        // A filter per source over PCM16 rows: the classes are handles of their own over f32 rows -- those of the converted copy, whose room is
+        // taken here (the classes keep the pointers) and which the first run fills
+        if (n_sources > p->cfg.max_sources) return RH_ERR_CAPACITY;
+        if (n_sources && !in_frames_host) return RH_ERR_INVALID;
+        p->h_pcm.assign(n_sources, SrcDesc{nullptr, 0, 0, 1.0f, {0, 0, 0}});
+        for (uint32_t s = 0; s < n_sources; ++s) {
+            if (in_frames_host[s] > p->cfg.max_in_frames) return RH_ERR_CAPACITY;
+            if (in_frames_host[s] && (!pcm_host[s] || (reinterpret_cast<uintptr_t>(pcm_host[s]) & 1u))) return RH_ERR_INVALID;
+            p->h_pcm[s].data = reinterpret_cast<const float *>(pcm_host[s]);
+            p->h_pcm[s].frames = (uint32_t)in_frames_host[s];
+        }
+        std::vector<const float *> rows;
+        rh_status st = pcm_alloc(p, &rows);
+        if (st == RH_OK) st = set_sources_classes(p, rows.data(), in_frames_host, n_sources);
+        if (st != RH_OK) {
+            (void)pcm_release(p);
+            return st;
+        }
+        p->pcm = true;
+        return RH_OK;
     }
     if (p && !p->cls.empty()) {  // back to the handle's one filter
         for (rh_rlm::FilterClass &c : p->cls)
             if (c.h) (void)rh_rlm_destroy(c.h);
         p->cls.clear();
     }
-    return set_sources_impl(p, srcs_host, in_frames_host, n_sources, nullptr);
+    return set_sources_impl(p, srcs_host, in_frames_host, n_sources, nullptr, pcm_host);
+}
+
+rh_status rh_rlm_set_sources(rh_rlm *p, const float *const *srcs_host, const uint64_t *in_frames_host, uint32_t n_sources) {
+    if (p && n_sources && !srcs_host) return RH_ERR_INVALID;
+    return set_sources_any(p, srcs_host, nullptr, in_frames_host, n_sources);
+}
+
+rh_status rh_rlm_set_sources_pcm16(rh_rlm *p, const int16_t *const *srcs_host, const uint64_t *in_frames_host, uint32_t n_sources) {
+    if (p && n_sources && !srcs_host) return RH_ERR_INVALID;
+    static const int16_t *const none[1] = {nullptr};
+    return set_sources_any(p, nullptr, srcs_host ? srcs_host : none, in_frames_host, n_sources);
+}
+
+rh_status rh_rlm_source_format(rh_rlm *p, int32_t *format, int32_t *native) {
+    if (!p || !format || !native) return RH_ERR_INVALID;
+    *format = p->pcm ? 1 : 0;
+    *native = p->pcm ? p->last_native : 0;
+    return RH_OK;
 }
 
 rh_status rh_rlm_set_filters(rh_rlm *p, const int32_t *kinds_host, const uint32_t *freqs_host, const float *qs_host, uint32_t n) {
@@ -817,6 +963,10 @@ rh_status rh_rlm_set_gains(rh_rlm *p, const float *gains_host, uint32_t n) {
         }
         RH_HIP_TRY(hipMemcpy(p->d_srcs, p->h_desc.data(), sizeof(SrcDesc) * p->n_sources, hipMemcpyHostToDevice));
         p->srcs_version += 1;
+        if (p->pcm && p->h_pcm.size() == p->n_sources) {  // the int16 rows' table carries the factors too (the f32 view: pcm_f32_ready uploads it again)
+            for (uint32_t s = 0; s < p->n_sources; ++s) p->h_pcm[s].gain = p->h_desc[s].gain;
+            RH_HIP_TRY(hipMemcpy(p->d_pcm, p->h_pcm.data(), sizeof(SrcDesc) * p->n_sources, hipMemcpyHostToDevice));
+        }
     }
     return RH_OK;
 }
@@ -833,6 +983,11 @@ static rh_status run_classes(rh_rlm *p, float *dst, uint64_t out_capacity_frames
     for (rh_rlm::FilterClass &c : p->cls)
         if (!c.members.empty() && c.out_frames) live.push_back(&c);
     if (live.empty()) return RH_OK;
+    if (p->pcm) {  // PCM16 sources: the classes read the converted copy
+        const rh_status c = pcm_convert(p, rh::as_stream(stream));
+        if (c != RH_OK) return c;
+    }
+    p->last_native = 0;
     p->cls_one_launch = false;
     if (live.size() == 1) return rh_rlm_run(live[0]->h, dst, out_capacity_frames, nullptr, stream);
     const size_t row = (size_t)((p->out_frames * C + 3) & ~3ull);
@@ -937,6 +1092,10 @@ rh_status rh_rlm_autotune(rh_rlm *p, float *dst, uint64_t out_capacity_frames, r
     RH_REQUIRE_INIT();
     if (!p || !dst) return RH_ERR_INVALID;
     if (!p->cls.empty()) {  // per-source filters: every class finds its own geometry (the last one's is reported)
+        if (p->pcm) {  // (the classes run on the converted copy of PCM16 sources)
+            const rh_status c = pcm_convert(p, rh::as_stream(stream));
+            if (c != RH_OK) return c;
+        }
         for (rh_rlm::FilterClass &c : p->cls) {
             if (c.members.empty()) continue;
             const rh_status st = rh_rlm_autotune(c.h, dst, out_capacity_frames, stream, frames_per_lane, ring_stages);

@@ -801,11 +801,22 @@ class ResampleLowpassMix:
         return {n: getattr(g, n) for n, _ in RlmGeometry._fields_}
 
     def set_sources(self, tensors):
+        """Device tensors of interleaved samples, all torch.float32 or all torch.int16 (16-bit PCM as it lies in a WAV data chunk:
+        rh_rlm_set_sources_pcm16 -- the same bits as converting first; source_format() tells whether a run read the PCM itself)."""
         n = len(tensors)
+        kinds = {str(t.dtype) for t in tensors}
+        if not kinds <= {"torch.float32", "torch.int16"}:
+            raise ValueError(f"set_sources takes float32 or int16 tensors, not {sorted(kinds)}")
+        if len(kinds) > 1:
+            raise ValueError("set_sources takes sources of one dtype: all float32 or all int16")
+        pcm16 = kinds == {"torch.int16"}
         self._keep = list(tensors)
         ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in tensors])
         frames = (C.c_uint64 * n)(*[t.numel() // self.channels for t in tensors])
-        check(lib.rh_rlm_set_sources(self._h, ptrs, frames, n), "rh_rlm_set_sources")
+        if pcm16:
+            check(lib.rh_rlm_set_sources_pcm16(self._h, ptrs, frames, n), "rh_rlm_set_sources_pcm16")
+        else:
+            check(lib.rh_rlm_set_sources(self._h, ptrs, frames, n), "rh_rlm_set_sources")
         # run() reports out_frames too; it is needed here to size the output allocation
         mx = 0
         for t in tensors:
@@ -814,6 +825,12 @@ class ResampleLowpassMix:
                                              self.channels, self.cfg.span_len, C.byref(o)), "rh_resample_out_frames")
             mx = max(mx, o.value)
         self.out_frames = mx
+
+    def source_format(self):
+        """{"format": 0 f32 rows / 1 PCM16 rows, "native": 1 = the last one-shot run read the PCM16 rows themselves}."""
+        f, nat = C.c_int32(0), C.c_int32(0)
+        check(lib.rh_rlm_source_format(self._h, C.byref(f), C.byref(nat)), "rh_rlm_source_format")
+        return {"format": f.value, "native": nat.value}
 
     def run(self, out=None):
         """Enqueue one pass on the current stream; returns the mixed [out_frames*channels] tensor."""
