@@ -430,6 +430,36 @@ rh_status rh_wide_mix_block_filtered(float *dst, uint32_t channels, uint32_t to_
                                      const rh_wide_src *srcs_host, uint32_t n_sources, const int32_t *kinds_host,
                                      const float *coeffs5_host, float *const *states_host, int32_t mode,
                                      void *scratch, uint64_t scratch_bytes, rh_stream stream);
+/* ---- A block of a mixer of SPATIAL EMITTERS in one launch: what SpatialPlayer feeds its mixer (spatial_player.rs:60-77, player.rs:121-166,
+ * mixer.rs:58-66).  dst receives out_frames frames of `channels` floats of the mix, in insertion order ((0 + v_0) + v_1) + ..., of
+ *     v_s = SampleRateConverter(Amplify(ChannelVolume(x_s)))
+ * ChannelVolume (channel_volume.rs:71-88; Spatial is one with two volumes): per source frame the mean ((0 + s0) + s1 + ..) / in_ch, and
+ * sample (f, c) of its output is that mean times the gain of channel c, then times the Amplify's factor.  `channels` is the number of
+ * volumes AND the mixer's channel count (an emitter with another number of volumes stays a chain of its own).  Gains and factors change
+ * by STEPS, by rh_channel_volume_steps' rule: sample (f, c), counted from `data`, has index k = f * channels + c in the adapter's output
+ * and takes gain entry (gain_first + k) / gain_period - gain_first / gain_period, column c, and factor entry (factor_first + k) /
+ * factor_period - factor_first / factor_period; a change in mid-frame reaches the later channels of that frame, and the two taps of one
+ * lerp may lie in different steps.  The converter is rh_wide_mix_block's: i = floor((phase + j F) / T), a + (b - a) * num / T over the
+ * scaled samples, the last frame verbatim, F == T passes through.  Bit-identical to rh_channel_volume_steps per source into rows and
+ * rh_wide_mix_block over the rows.
+ * A source is an rh_wide_src with `channels` = its own channel count (in_ch), data / from_rate / phase / frames / last as
+ * rh_wide_mix_block reads them, and gain == 1 (its Amplify is the factor table).  Its tables travel as host arrays parallel to
+ * srcs_host, read before the call returns:
+ *   gains_dev_host     per source a DEVICE pointer to [entries][channels] floats
+ *   gain_steps_host    3 words a source: {gain_first, gain_period, entries}
+ *   factors_dev_host   per source a DEVICE pointer to [entries] floats; NULL (the entry or the whole array): no Amplify
+ *   factor_steps_host  3 words a source: {factor_first, factor_period, entries} (not read where there are no factors)
+ * A table covers the samples of the source frames the block's taps touch, counted from `data`.  Rows and tables need 4-byte alignment
+ * only.  A source with frames == 0 is not looked at (data and tables may be NULL).  n_sources == 0 writes zeros.  No host
+ * synchronisation, no allocation; launches per block: one per 32 sources, times two where a source ends inside a block of mono sources of
+ * one rate into an 8-byte-aligned stereo dst (the frames in front of the end take the kernel that loads a tap once for both ears).
+ * RH_ERR_INVALID, nothing written: what rh_wide_mix_block refuses of the shared fields, channels == 0 or > 16, an in_ch of 0, a gain other
+ * than 1, a period of 0, gains NULL for a source with frames > 0, a table shorter than the block reaches.  A block so long that
+ * phase + j F (or a sample index of the step rule) leaves 32 bits is cut into launches. */
+rh_status rh_spatial_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
+                               const rh_wide_src *srcs_host, uint32_t n_sources, const float *const *gains_dev_host,
+                               const uint64_t *gain_steps_host, const float *const *factors_dev_host,
+                               const uint64_t *factor_steps_host, rh_stream stream);
 
 /* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
  * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays

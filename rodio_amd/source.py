@@ -643,6 +643,53 @@ def wide_mix_block_filtered(dst, channels, to_rate, out_frames, srcs, filters, m
     return dst
 
 
+class SpatialSrc:
+    """One emitter of spatial_mix_block: a source as rh_wide_mix_block reads it (data: a float32 device tensor or a device address; in_ch,
+    from_rate, phase, frames, last) with ChannelVolume's volumes by steps (gains: a float32 device tensor [entries, channels] or a device
+    address with n_gains; gain_first, gain_period) and the Amplify behind it (factors: [entries] or None; factor_first, factor_period)."""
+
+    def __init__(self, data, in_ch, from_rate, frames, gains, gain_period, gain_first=0, factors=None, factor_period=1, factor_first=0, phase=0,
+                 last=0xFFFFFFFF, n_gains=None, n_factors=None):
+        self.data, self.in_ch, self.from_rate, self.phase, self.frames, self.last = data, int(in_ch), int(from_rate), int(phase), int(frames), int(last)
+        self.gains, self.gain_first, self.gain_period, self.n_gains = gains, int(gain_first), int(gain_period), n_gains
+        self.factors, self.factor_first, self.factor_period, self.n_factors = factors, int(factor_first), int(factor_period), n_factors
+
+
+def spatial_mix_block(dst, channels, to_rate, out_frames, srcs):
+    """rh_spatial_mix_block: a block of a mixer of spatial emitters in one launch -- per source SampleRateConverter(Amplify(ChannelVolume(x)))
+    with the volumes and the factor changing by steps, and the ordered sum.  dst: a float32 device tensor of out_frames * channels
+    elements (or a device address); srcs: SpatialSrc objects in insertion order."""
+    _ensure()
+    n = len(srcs)
+    arr = (_lib.WideSrc * max(n, 1))()
+    gains, factors = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    gsteps, fsteps = (C.c_uint64 * (3 * max(n, 1)))(), (C.c_uint64 * (3 * max(n, 1)))()
+
+    def table(t, entries, width, who):
+        """(address, entries) of a step table: a contiguous float32 CUDA tensor of whole entries, or an address with its count"""
+        if t is None:
+            return None, 0
+        if isinstance(t, int):
+            if entries is None:
+                raise ValueError(f"spatial_mix_block: {who} given as an address needs its number of entries")
+            return t, int(entries)
+        torch = _t()
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() % width:
+            raise ValueError(f"spatial_mix_block: {who} must be a contiguous float32 CUDA tensor of whole entries of {width}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.data_ptr(), (t.numel() // width if entries is None else int(entries))
+
+    for k, s in enumerate(srcs):
+        arr[k].data = s.data if isinstance(s.data, int) or s.data is None else s.data.data_ptr()
+        arr[k].channels, arr[k].from_rate, arr[k].phase, arr[k].frames, arr[k].last, arr[k].gain = s.in_ch, s.from_rate, s.phase, s.frames, s.last, 1.0
+        gains[k], gsteps[3 * k + 2] = table(s.gains, s.n_gains, channels, "gains")
+        gsteps[3 * k], gsteps[3 * k + 1] = s.gain_first, s.gain_period
+        factors[k], fsteps[3 * k + 2] = table(s.factors, s.n_factors, 1, "factors")
+        fsteps[3 * k], fsteps[3 * k + 1] = s.factor_first, s.factor_period
+    check(lib.rh_spatial_mix_block(C.c_void_p(dst) if isinstance(dst, int) else _ptr(dst), channels, to_rate, out_frames, arr, n, gains, gsteps, factors, fsteps, _stream()),
+          "rh_spatial_mix_block")
+    return dst
+
+
 def delay_samples(ns, rate, ch) -> int:
     return int(lib.rh_delay_samples(ns, rate, ch))
 
