@@ -11,6 +11,10 @@
  *   - Audio is interleaved f32 (`Sample = f32`, src/common.rs:36,48; src/source/mod.rs:131-135).
  *   - All data pointers are DEVICE pointers owned by the caller unless the name ends in _host.
  *     Small parameter arrays (gains, coefficients) are HOST pointers and are copied by value.
+ *     Every host array of an entry that takes a stream (tables of sources, addresses, starts, lengths, segments, pairs,
+ *     coefficients, parameter structures) is read before the call returns: the caller may rewrite it at once, whatever is still
+ *     queued on the stream.  The one exception is a page-locked block given to rh_memcpy_h2d / rh_memcpy_h2d_rows (see there).
+ *     (tests/test_gpu_stream_order.py: every such array overwritten behind the call while the stream is held back.)
  *   - Every function enqueues on `stream` (a hipStream_t passed as void*; NULL = default
  *     stream) and returns an rh_status; nothing throws or aborts.  End of stream (`None`) is
  *     expressed through returned lengths, never through an error.
@@ -71,9 +75,13 @@ rh_status rh_async_status(void);
 rh_status rh_malloc(void **out, size_t bytes);
 rh_status rh_free(void *p);
 rh_status rh_memset(void *p, int32_t value, size_t bytes, rh_stream stream);
+/* Host blocks of the two uploads: a page-locked block (rh_host_alloc) is read when `stream` reaches the copy, so it stays untouched
+ * until then, and the call never waits.  A pageable block is read before the call returns, and the call may wait for it. */
 rh_status rh_memcpy_h2d(void *dst, const void *src_host, size_t bytes, rh_stream stream);
-/* `rows` rows of `width_bytes` each, `pitch_bytes` apart on both sides: a block of staged rows without the unused ends. */
+/* `rows` rows of `width_bytes` each, `pitch_bytes` apart on both sides: a block of staged rows without the unused ends.
+ * From a pageable block this call waits until `stream` has run everything queued before it (the runtime's pitched copy does). */
 rh_status rh_memcpy_h2d_rows(void *dst, const void *src_host, size_t pitch_bytes, size_t width_bytes, size_t rows, rh_stream stream);
+/* Waits until `stream` has run the copy: the host block holds the data when the call returns. */
 rh_status rh_memcpy_d2h(void *dst_host, const void *src, size_t bytes, rh_stream stream);
 /* For a pull-model shim (include/rodio_hip.hpp): page-locked host blocks, copies that do not synchronise. */
 rh_status rh_memcpy_d2h_async(void *dst_host, const void *src, size_t bytes, rh_stream stream);
@@ -84,9 +92,10 @@ rh_status rh_stream_create(rh_stream *out);
 rh_status rh_stream_destroy(rh_stream s);
 rh_status rh_stream_synchronize(rh_stream s);
 /* The scan kernels (rh_limit, rh_biquad mode 1, rh_agc) keep a scratch buffer per stream, grown on demand and reused by every
- * later launch on that stream; rh_stream_destroy frees it for the library's own streams.  For a stream of the caller's (a
- * PyTorch stream, ...) that is about to be destroyed: synchronises it and frees its buffer (a handle value the runtime
- * recycles must not inherit one). */
+ * later launch on that stream (rh_noise_generate and rh_crossfade use it too).  The call that makes it grow synchronises the
+ * stream first: a first call of a larger shape waits, the calls after it do not.  rh_stream_destroy frees the buffer for the
+ * library's own streams.  For a stream of the caller's (a PyTorch stream, ...) that is about to be destroyed: synchronises it and
+ * frees its buffer (a handle value the runtime recycles must not inherit one). */
 rh_status rh_stream_release_scratch(rh_stream s);
 /* HIP-event timing on `stream` (bench.py measures the kernels on the stream they run on). */
 rh_status rh_event_create(void **out);
@@ -496,6 +505,8 @@ rh_status rh_uniform_row(float *dst, uint64_t dst_capacity, const float *src, ui
  *   [4] b: device address of the row in its own format         [5] b_samples   [6] b_channels   [7] b_rate
  *   [8] b_span_len: current_span_len() of b, 0 = None          [9] dst: device address         [10] dst_capacity, in samples */
 enum { RH_CROSSFADE_PAIR_WORDS = 11 };
+/* rh_crossfade stages its table in a ring of four page-locked slots per stream: of calls queued back to back on a stream that is
+ * backed up, the fifth waits until the copy of the first has run. */
 rh_status rh_crossfade_out_samples(const uint64_t *pair_host, uint64_t duration_ns, uint64_t *out_samples);
 rh_status rh_crossfade(const uint64_t *pairs_host, uint32_t n_pairs, uint64_t duration_ns, uint64_t *out_samples_host,
                        rh_stream stream);
@@ -510,7 +521,9 @@ rh_status rh_crossfade(const uint64_t *pairs_host, uint32_t n_pairs, uint64_t du
  *          (dst, src, and frames*channels % 4 == 0 for n_streams > 1), more than 8 channels, a filter that does not forget
  *          within 64 tiles, dst == src (the scan reads the two frames in front of every share after a neighbour may have
  *          overwritten them) -- runs in mode 0 instead: never an error, the exact bits, slower.
- * The batch form filters n_streams equally shaped blocks laid out back to back.  Mode 0 works in place. */
+ * The batch form filters n_streams equally shaped blocks laid out back to back.  Mode 0 works in place.
+ * Mode 1 keeps the device tables of its 32 most recent filters; a call with a 33rd frees the oldest, and that free may wait for the
+ * device. */
 rh_status rh_biquad_coeffs(int32_t kind, uint32_t freq, float q, uint32_t sample_rate,
                            float out_coeffs5[5]);
 rh_status rh_biquad(float *dst, const float *src, uint64_t frames, uint32_t channels,
@@ -612,7 +625,8 @@ rh_status rh_rlm_create(rh_rlm **out, const rh_rlm_config *cfg);
 rh_status rh_rlm_destroy(rh_rlm *p);
 /* srcs_host[s] = device pointer of source s ([in_frames_host[s]][channels] f32, 16-byte
  * aligned).  All sources start at mixer time 0.  dst holds out_capacity_frames*channels
- * samples; *out_frames = max over sources of the resampled length. */
+ * samples; *out_frames = max over sources of the resampled length.
+ * On a handle that has run, rh_rlm_set_sources and rh_rlm_set_sources_pcm16 wait until everything the handle has queued on its stream has completed. */
 rh_status rh_rlm_set_sources(rh_rlm *p, const float *const *srcs_host,
                              const uint64_t *in_frames_host, uint32_t n_sources);
 /* srcs_host[s] = device pointer of source s as interleaved signed 16-bit PCM ([in_frames_host[s]][channels] int16_t, the layout of a
@@ -679,7 +693,9 @@ rh_status rh_rlm_run_subset(rh_rlm *p, uint32_t first, uint32_t count, float *ds
  * cfg.span_len != 0: every source reports spans of that many samples (a SamplesBuffer longer than 32 768 samples: any
  * span_len >= 32768): the converter restarts every min(span_len, 32768) samples at the same frames of every source
  * (uniform.rs:56-67), each span's last frame verbatim.  Sources with other span patterns: rh_uniform_segments in front of a
- * pass-through stream (from_rate == to_rate), which is what include/rodio_hip.hpp does.  One set of sources per stream. */
+ * pass-through stream (from_rate == to_rate), which is what include/rodio_hip.hpp does.  One set of sources per stream.
+ * Both block entries stage their descriptors in a ring of four page-locked slots per handle: of blocks queued back to back on a
+ * stream that is backed up, the fifth waits until the copy of the first has run. */
 rh_status rh_rlm_stream_begin(rh_rlm *p);
 rh_status rh_rlm_stream_block(rh_rlm *p, const float *const *srcs_host, uint32_t n_sources,
                               uint64_t avail_frames, int32_t flush, float *dst,

@@ -14,6 +14,10 @@ reference and the two outputs equal each other bit for bit (`same_under_fills`) 
 under one of them.  A destination between fills (`check_filled`): under each fill every guard and gap byte is untouched and the row equals
 the reference -- an element that was never written still holds the fill, which equals the reference under at most one of the two.
 
+Gate mode (tests/stream_gate.py, test_gpu_stream_order.py): `stage()` keeps an arena's content aside and leaves GARBAGE (a third NaN) in the
+live buffer; `restore_on`, `snapshot_on` and `spoil_on` queue copies and fills on the stream under test, and `check_snapshot` /
+`snapshot_unchanged` are the checks above on the snapshot.  `spoil_host` is what a host table gets once its call has returned.
+
 The layouts and the checkers are pure numpy (tests/test_arena_cpu.py holds them on arrays spoiled by hand); only `Arena` and `ByteArena`
 touch torch."""
 import numpy as np
@@ -114,9 +118,51 @@ def same(a, b):
     return a.shape == b.shape and bool(np.array_equal(bits(a), bits(b)))
 
 
-class Arena:
+GARBAGE = 0x7FC0DEAD  # gate mode: a third quiet NaN, what a live buffer holds outside the gated window
+GARBAGE_BYTE = 0xFF  # ... of a byte arena: a NaN at every byte shift of a float, -1 in every integer type
+HOST_GARBAGE_BYTE = 0xA5  # ... and a host array after the call it was given to has returned
+
+
+class _Gated:
+    """Gate mode (the section below): stage() / restore_on / snapshot_on / spoil_on for Arena and ByteArena.  Every device operation is
+    queued on the given torch stream and none synchronises; snapshot() is read after the caller has synchronised."""
+
+    def stage(self):
+        """Keep the buffer's present content as the staged copy (and as `initial`) and fill the live buffer with garbage."""
+        self.staged = self.buf.clone()
+        self.snap = self.buf.clone()
+        self.initial = self.staged.cpu().numpy().view(self.initial.dtype)
+        self.buf.fill_(self._garbage)
+        self.snap.fill_(self._garbage)
+        return self
+
+    def restore_on(self, stream):
+        import torch
+
+        with torch.cuda.stream(stream):
+            self.buf.copy_(self.staged, non_blocking=True)
+
+    def snapshot_on(self, stream):
+        import torch
+
+        with torch.cuda.stream(stream):
+            self.snap.copy_(self.buf, non_blocking=True)
+
+    def spoil_on(self, stream):
+        import torch
+
+        with torch.cuda.stream(stream):
+            self.buf.fill_(self._garbage)
+
+    def snapshot(self):
+        """The snapshot's words (bytes for a ByteArena): call after the stream has been synchronised."""
+        return self.snap.cpu().numpy().view(self.initial.dtype)
+
+
+class Arena(_Gated):
     """A layout on the device.  ptr(r) is the address of row r; words() copies the buffer back; check() is check() on that copy;
     unchanged() holds the buffer against what was uploaded (sources, function tables: nothing may write them)."""
+    _garbage = GARBAGE
 
     def __init__(self, lay, rows=None):
         import torch
@@ -145,6 +191,56 @@ class Arena:
         w = self.words()
         bad = np.flatnonzero(w != self.initial)
         assert bad.size == 0, f"a read-only arena was written: {bad.size} word(s), the first at {_where(self.layout, int(bad[0]))}"
+
+    # gate mode (below): the same checks on the snapshot
+    def check_snapshot(self, written=None, dtype=np.float32):
+        return check(self.snapshot(), self.layout, written).view(dtype)
+
+    def snapshot_unchanged(self):
+        check_unchanged(self.snapshot(), self.initial, self.layout)
+
+
+# ---- gate mode (tests/stream_gate.py): an arena whose content arrives on the stream under test ------------------------------------------------
+# The live buffer holds GARBAGE until a device copy queued on the gated stream puts the staged content in place; what the entry left is
+# copied to a snapshot on the same stream, the live buffer is spoiled again behind it, and the checks read the snapshot.  A launch that ran
+# on another stream ran too early (it read garbage, and the restore wiped what it stored) or too late (it read garbage again).
+
+
+def spoil_host(a, value=None):
+    """Overwrite a host array (numpy or ctypes) in place after the call that was given it has returned: every byte HOST_GARBAGE_BYTE, or
+    every element `value` -- for tables of device addresses, counts and lengths, where the garbage must be one that cannot send a late
+    reader out of bounds (the address of a pit of NaN, a length of 0).  Returns the array."""
+    import ctypes
+
+    if isinstance(a, np.ndarray):
+        assert a.flags.writeable and a.flags.c_contiguous
+        if value is None:
+            a.reshape(-1).view(np.uint8)[:] = HOST_GARBAGE_BYTE
+        else:
+            a[...] = value
+    elif value is None or value == 0:  # (zero also for arrays of structures)
+        ctypes.memset(ctypes.addressof(a), HOST_GARBAGE_BYTE if value is None else 0, ctypes.sizeof(a))
+    else:
+        for i in range(len(a)):
+            a[i] = value
+    return a
+
+
+def host_bytes(a):
+    """The bytes of a host array (numpy or ctypes) as they lie in memory, a copy."""
+    import ctypes
+
+    if isinstance(a, np.ndarray):
+        return np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()
+    return np.frombuffer(ctypes.string_at(ctypes.addressof(a), ctypes.sizeof(a)), np.uint8).copy()
+
+
+def check_unchanged(words, initial, lay, where=_where):
+    """A read-only arena's words (or bytes) against what was staged."""
+    w, initial = np.asarray(words), np.asarray(initial)
+    assert w.shape == initial.shape and w.dtype == initial.dtype
+    bad = np.flatnonzero(w != initial)
+    assert bad.size == 0, f"a read-only arena was written: {bad.size} element(s), the first at {where(lay, int(bad[0]))}"
 
 
 def dst_arena(n, lead=0, dtype=np.float32):
@@ -304,8 +400,15 @@ def same_under_fills(outs, ref, tol=0.0, fills=FILLS):
     assert bad.size == 0, f"the row depends on its surroundings: {bad.size} byte(s) differ between the two fills, the first at byte {int(bad[0])}"
 
 
-class ByteArena:
+class ByteArena(_Gated):
     """A byte layout on the device; the same calls as Arena.  check(ref_rows) is check_filled on the bytes copied back."""
+    _garbage = GARBAGE_BYTE
+
+    def check_snapshot(self, ref_rows, written=None, dtype=np.uint8):
+        return check_filled(self.snapshot(), self.layout, ref_rows, written).view(dtype)
+
+    def snapshot_unchanged(self):
+        check_unchanged(self.snapshot(), self.initial, self.layout, _where_bytes)
 
     def __init__(self, lay, rows=None):
         import torch

@@ -244,3 +244,65 @@ def test_same_compares_bits_and_flattens():
     b = a.copy()
     b.view(np.uint32)[0, 1] = arena.SENTINEL
     assert not arena.same(a, b)  # two NaNs of different payloads
+
+
+# ---- gate mode: the pure parts (the device parts run in test_gpu_stream_order.py, whose control shows that the gate can fail) --------------------
+def test_the_three_nans_differ_and_garbage_is_neither_sentinel():
+    w = np.array([arena.SENTINEL, arena.POISON, arena.GARBAGE], np.uint32)
+    assert np.isnan(w.view(np.float32)).all() and len(set(w.tolist())) == 3
+    assert arena.GARBAGE < 2**31  # it fills an int32 tensor
+    assert arena.GARBAGE_BYTE not in arena.FILLS and arena.HOST_GARBAGE_BYTE not in arena.FILLS
+    # a row that was written with garbage counts as written, one that the restore wiped does not: what the control relies on
+    lay = arena.layout(16)
+    w = arena.build(lay)
+    with pytest.raises(AssertionError, match="never written: 16 word"):
+        arena.check(w, lay)
+    w[lay.starts[0]: lay.starts[0] + 16] = arena.GARBAGE
+    assert np.isnan(arena.check(w, lay).view(np.float32)).all()
+
+
+def test_spoil_host_overwrites_numpy_and_ctypes_arrays_in_place():
+    import ctypes as C
+
+    a = np.arange(6, dtype=np.float32).reshape(2, 3)
+    keep = a
+    assert arena.spoil_host(a) is keep and np.all(arena.host_bytes(a) == arena.HOST_GARBAGE_BYTE) and not np.any(a == np.arange(6, dtype=np.float32).reshape(2, 3))
+    t = (C.c_uint64 * 5)(1, 2, 3, 4, 5)
+    arena.spoil_host(t)
+    assert list(t) == [0xA5A5A5A5A5A5A5A5] * 5 and arena.host_bytes(t).size == 40
+    # tables of addresses and lengths: an element value that cannot send a late reader out of bounds
+    p = (C.c_void_p * 3)(0x1000, 0x2000, 0x3000)
+    arena.spoil_host(p, 0x7000)
+    assert [p[i] for i in range(3)] == [0x7000] * 3
+    n = np.array([5, 6, 7], np.uint64)
+    arena.spoil_host(n, 0)
+    assert not n.any()
+    with pytest.raises(AssertionError):
+        arena.spoil_host(np.arange(10)[::2])  # not the array the call was given
+
+
+def test_check_unchanged_names_the_first_word_that_differs():
+    lay = arena.layout(100, 1, arena.POISON)
+    w = arena.build(lay, [np.arange(100, dtype=np.float32)])
+    arena.check_unchanged(w.copy(), w, lay)
+    bad = w.copy()
+    bad[lay.starts[0] + 7] = arena.GARBAGE
+    with pytest.raises(AssertionError, match=r"read-only arena was written: 1 element.*offset \+7 relative to row 0"):
+        arena.check_unchanged(bad, w, lay)
+    bl = arena.layout_bytes(10, 3)
+    b = arena.build_bytes(bl, [np.arange(10, dtype=np.uint8)])
+    bad = b.copy()
+    bad[bl.starts[0] - 1] = 0
+    with pytest.raises(AssertionError, match=r"byte offset -1 relative to row 0"):
+        arena.check_unchanged(bad, b, bl, arena._where_bytes)
+
+
+def test_a_kit_spoils_the_host_arrays_of_the_call_that_returned_and_forgets_them():
+    import stream_gate
+
+    k = stream_gate.Kit()
+    a, b = k.host(np.ones(4, np.float32)), k.host(np.array([3, 4], np.uint64), 0)
+    k.spoil_hosts()
+    assert np.all(arena.host_bytes(a) == arena.HOST_GARBAGE_BYTE) and not b.any() and k.fresh == []
+    c = stream_gate.case([len], print)
+    assert c.warm == c.calls == [len] and c.rewind is None and stream_gate.case([len], print, warm=[id]).warm == [id]
