@@ -411,6 +411,29 @@ typedef struct rh_wide_src {
 } rh_wide_src;
 rh_status rh_wide_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
                             const rh_wide_src *srcs_host, uint32_t n_sources, rh_stream stream);
+/* ... the current block of MANY such mixers in ONE launch: rooms of a voice server, zones of a game world, stems rendered side by side.
+ * Mixer b (b < n_mixers) has the destination dsts_host[b] (a device pointer), channels_host[b] channels, the rate to_rates_host[b], a
+ * block of out_frames_host[b] frames and src_counts_host[b] sources in insertion order; srcs_host holds the sources of all mixers back to
+ * back -- mixer 0's, then mixer 1's, and so on: src_counts_host[0] + .. + src_counts_host[n_mixers - 1] entries, each read exactly as
+ * rh_wide_mix_block reads it.  dsts_host[b] receives the bits that
+ *     rh_wide_mix_block(dsts_host[b], channels_host[b], to_rates_host[b], out_frames_host[b], <its sources>, src_counts_host[b], stream)
+ * writes: the same operations in the same order per output sample.  A mixer with out_frames == 0 is skipped (its dst may be NULL, nothing
+ * else of it is looked at); one without sources gets zeros; a source with frames == 0 is not looked at; n_mixers == 0 does nothing.  Rows
+ * and destinations need 4-byte alignment only.  The destinations of different mixers must not overlap: the caller's promise, not checked.
+ * The six host arrays are read before the call returns.  On `stream`: one copy of the call's tables (from page-locked memory of the
+ * library's, into the stream's scratch) and ONE launch, for any number of mixers and any number of sources or rates per mixer; a call
+ * whose mixers all have out_frames == 0 queues nothing, and a call of ONE mixer for which rh_wide_mix_block takes one launch (up to 32
+ * sources of up to four (rate, phase) pairs, no alike sources of which one ends inside the block) is that launch, without the copy: still
+ * one launch a call.  A warmed call neither waits for the stream nor allocates (the first calls on a
+ * stream, and a call with larger tables than any before it, do; the fifth call in a row waits until the copy of the first has run).
+ * RH_ERR_INVALID, nothing written by any mixer: a NULL array with n_mixers > 0 (srcs_host only where a count is not 0); and of a mixer with
+ * out_frames > 0: a NULL dst, channels or to_rate of 0, and what rh_wide_mix_block refuses of a source (frames > 0 with data == NULL, channels
+ * or from_rate of 0, frames > out_frames, phase >= T).  RH_ERR_UNSUPPORTED, nothing written: F * T beyond 32 bits; out_frames > 0x7fffffff;
+ * a block so long that a source's phase + j F leaves 32 bits, i.e. out_frames > (2^32 - 1 - T) / F -- rh_wide_mix_block cuts such a block
+ * into launches, blocks handed over in batches are short; more than 2^31 - 1 tiles of work. */
+rh_status rh_wide_mix_batch(float *const *dsts_host, const uint32_t *channels_host, const uint32_t *to_rates_host,
+                            const uint64_t *out_frames_host, const uint32_t *src_counts_host, uint32_t n_mixers,
+                            const rh_wide_src *srcs_host, rh_stream stream);
 /* ... with a low_pass / high_pass on any of its sources: mixer.add(src, gain, filter) of a mixer of more than two channels, a block at a
  * time.  Source s enters the ordered sum as y_s = BltFilter(UniformSourceIterator(Amplify(x_s))) at the mixer's rate and channel count
  * (mixer.rs:58-66, blt.rs:397-492); an unfiltered one as rh_wide_mix_block takes it.  A filtered source that ends inside the block is

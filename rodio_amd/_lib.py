@@ -137,6 +137,7 @@ SIGNATURES = {
     "rh_uniform_segments_dev": (i32, [vp, u32, u64, vp]),
     "rh_mix_sum": (i32, [vp, sz, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), u32, vp]),
     "rh_wide_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, vp]),
+    "rh_wide_mix_batch": (i32, [C.POINTER(vp), C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u32), u32, C.POINTER(WideSrc), vp]),
     "rh_wide_mix_filtered_scratch_bytes": (i32, [u32, u64, u32, C.POINTER(u64)]),
     "rh_wide_mix_block_filtered": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(i32), f32p, C.POINTER(vp), i32, vp, u64, vp]),
     "rh_spatial_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), vp]),

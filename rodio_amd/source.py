@@ -690,6 +690,28 @@ def spatial_mix_block(dst, channels, to_rate, out_frames, srcs):
     return dst
 
 
+def wide_mix_batch(dsts, channels, to_rates, out_frames, srcs):
+    """rh_wide_mix_batch: the current block of many mixers of any channel count in ONE launch; every mixer gets the bits rh_wide_mix_block
+    writes for it.  dsts: per mixer a float32 device tensor of out_frames * channels elements, a device address, or None (out_frames == 0);
+    channels, to_rates, out_frames: per mixer; srcs: per mixer a sequence of `_lib.WideSrc` in insertion order (a ctypes array or a list)."""
+    _ensure()
+    n = len(dsts)
+    if not (len(channels) == len(to_rates) == len(out_frames) == len(srcs) == n):
+        raise ValueError("wide_mix_batch: dsts, channels, to_rates, out_frames and srcs must have one entry per mixer")
+    d = (C.c_void_p * max(n, 1))(*[x if isinstance(x, int) or x is None else x.data_ptr() for x in dsts])
+    ch, rates = (C.c_uint32 * max(n, 1))(*map(int, channels)), (C.c_uint32 * max(n, 1))(*map(int, to_rates))
+    frames, counts = (C.c_uint64 * max(n, 1))(*map(int, out_frames)), (C.c_uint32 * max(n, 1))(*[len(s) for s in srcs])
+    total = sum(len(s) for s in srcs)
+    table = (_lib.WideSrc * max(total, 1))()
+    at = 0
+    for s in srcs:  # all mixers' sources back to back
+        for x in s:
+            C.memmove(C.byref(table, at * C.sizeof(_lib.WideSrc)), C.byref(x), C.sizeof(_lib.WideSrc))
+            at += 1
+    check(lib.rh_wide_mix_batch(d, ch, rates, frames, counts, n, table, _stream()), "rh_wide_mix_batch")
+    return dsts
+
+
 def delay_samples(ns, rate, ch) -> int:
     return int(lib.rh_delay_samples(ns, rate, ch))
 
