@@ -492,6 +492,44 @@ rh_status rh_spatial_mix_block(float *dst, uint32_t channels, uint32_t to_rate, 
                                const rh_wide_src *srcs_host, uint32_t n_sources, const float *const *gains_dev_host,
                                const uint64_t *gain_steps_host, const float *const *factors_dev_host,
                                const uint64_t *factor_steps_host, rh_stream stream);
+/* ---- A block of a mixer of PLAYERS in one launch: what Player::append feeds its mixer (player.rs:121-166, mixer.rs:58-66) when the sound
+ * it is handed is a fade_in, a fade_out or a linear_gain_ramp.  dst receives out_frames frames of `channels` floats of the mix, in insertion
+ * order ((0 + v_0) + v_1) + ..., of
+ *     v_s = ChannelCountConverter(SampleRateConverter(Amplify_steps(LinearGainRamp(Amplify_gain(x_s)))))
+ * A source is an rh_wide_src read exactly as rh_wide_mix_block reads it (data / channels / from_rate / phase / frames / last; rows need
+ * 4-byte alignment only); `gain` is the innermost Amplify, and from_rate is the rate the mixer sees, i.e. behind `speed` (speed.rs relabels
+ * it).  Per tap, each a rounded f32 multiply of its own: x * gain, always; * the ramp's factor, where the source has a ramp; * the stepped
+ * factor, where it has a table.  Then rh_wide_mix_block's converter -- i = floor((phase + j F) / T), a + (b - a) * num / T with the IEEE
+ * division, the last frame verbatim, F == T passes through -- and the channel rule of channels.rs:57-85.  The adapters travel as host
+ * arrays parallel to srcs_host, all read before the call returns:
+ *   ramps_host         4 words a source: {kind, duration_ns, first_frame, rate}.  kind 0: no ramp, the sample is not multiplied; 1: a
+ *                      LinearGainRamp with clamp_end false (fade_in, linear_gain_ramp(.., false)); 2: one with clamp_end true (fade_out).
+ *                      rate is the rate the ramp counts time at: the source's own rate IN FRONT OF `speed` (it differs from from_rate
+ *                      whenever speed != 1).  first_frame = the frames of the adapter's stream in front of `data`: source frame i,
+ *                      counted from data, takes the factor rh_linear_gain_ramp gives frame first_frame + i (linear_ramp.rs:79-110; the same
+ *                      for every channel of a frame).  A duration of 0 is a ramp that has run out: 1, or end_gain with clamp_end.
+ *                      NULL: no source has a ramp.
+ *   ramp_gains_host    2 floats a source: {start_gain, end_gain}; not read where kind is 0; may be NULL where every kind is 0.
+ *   factors_dev_host   per source a DEVICE pointer to [entries] floats; NULL (the entry or the whole array): no stepped Amplify
+ *   factor_steps_host  3 words a source: {first, period, entries} (not read where there are no factors).  Sample k = f * src_channels + c
+ *                      of the source's stream, counted from data, takes entry (first + k) / period - first / period: rh_amplify_steps'
+ *                      rule.  A change may fall between the channels of a frame, and the two taps of one lerp may lie in different steps.
+ *                      A table covers the samples up to the last one a tap of the block reads.
+ * Bit-identical to the chain it replaces: per source rh_amplify -> rh_linear_gain_ramp (sample_offset = first_frame * channels) ->
+ * rh_amplify_steps into a row, then rh_wide_mix_block over the rows with gain 1.  A source with frames == 0 is not looked at (its pointers
+ * may be NULL); n_sources == 0 writes zeros; out_frames == 0 does nothing.  No host synchronisation, no allocation; one launch per 32
+ * sources (earlier where a fifth (rate, phase) pair comes up), later launches continue from the stored partial sum.  A ramp that has run
+ * out before the block's first frame costs the kernel one constant.
+ * RH_ERR_INVALID, nothing written: what rh_wide_mix_block refuses of the shared fields, a kind above 2, a ramp rate of 0 (or beyond 32
+ * bits), a ramp without ramp_gains_host, factors without factor_steps_host, a factor period of 0, a factor table shorter than the block's
+ * taps reach.  RH_ERR_UNSUPPORTED, nothing written: F * T beyond 32 bits; out_frames > 0x7fffffff; a block so long that a source's
+ * phase + j F leaves 32 bits, i.e. out_frames > (2^32 - 1 - T) / F; a source with a factor table of which the block's taps reach more than
+ * 2^30 samples.  Such blocks are refused, not cut into launches: blocks are short. */
+rh_status rh_player_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
+                              const rh_wide_src *srcs_host, uint32_t n_sources,
+                              const uint64_t *ramps_host, const float *ramp_gains_host,
+                              const float *const *factors_dev_host, const uint64_t *factor_steps_host,
+                              rh_stream stream);
 
 /* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
  * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays

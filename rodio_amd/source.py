@@ -690,6 +690,59 @@ def spatial_mix_block(dst, channels, to_rate, out_frames, srcs):
     return dst
 
 
+RAMP_KINDS = {None: 0, "none": 0, "ramp": 1, "fade_in": 1, "clamp": 2, "fade_out": 2}
+
+
+class PlayerSrc:
+    """One source of player_mix_block: a source as rh_wide_mix_block reads it (data: a float32 device tensor or a device address; channels,
+    from_rate -- the rate behind `speed` --, phase, frames, last, gain: the innermost Amplify) with the two adapters a Player's sound carries:
+    a LinearGainRamp (ramp: None, "ramp" / "fade_in" / 1 = clamp_end false, "clamp" / "fade_out" / 2 = clamp_end true; ramp_ns, start_gain,
+    end_gain, first_frame = frames of the ramp's stream in front of data, ramp_rate = the rate in FRONT of `speed`, from_rate by default;
+    fade_in and fade_out bring their gains) and the Amplify under periodic_access (factors: [entries] float32 device tensor, or an address
+    with n_factors, or None; factor_first, factor_period)."""
+
+    def __init__(self, data, channels, from_rate, frames, gain=1.0, ramp=None, ramp_ns=0, start_gain=None, end_gain=None, first_frame=0, ramp_rate=None,
+                 factors=None, factor_period=1, factor_first=0, phase=0, last=0xFFFFFFFF, n_factors=None):
+        self.data, self.channels, self.from_rate, self.phase, self.frames, self.last, self.gain = data, int(channels), int(from_rate), int(phase), int(frames), int(last), float(gain)
+        self.kind = RAMP_KINDS[ramp] if ramp in RAMP_KINDS else int(ramp)
+        preset = {"fade_in": (0.0, 1.0), "fade_out": (1.0, 0.0)}.get(ramp, (1.0, 1.0))
+        self.ramp_ns, self.first_frame, self.ramp_rate = int(ramp_ns), int(first_frame), int(from_rate if ramp_rate is None else ramp_rate)
+        self.start_gain, self.end_gain = float(preset[0] if start_gain is None else start_gain), float(preset[1] if end_gain is None else end_gain)
+        self.factors, self.factor_first, self.factor_period, self.n_factors = factors, int(factor_first), int(factor_period), n_factors
+
+
+def player_mix_block(dst, channels, to_rate, out_frames, srcs):
+    """rh_player_mix_block: a block of a mixer of Players in one launch -- per source the gain, the LinearGainRamp, the stepped Amplify,
+    the converter to the mixer's rate and layout, and the ordered sum.  dst: a float32 device tensor of out_frames * channels elements
+    (or a device address); srcs: PlayerSrc objects in insertion order."""
+    _ensure()
+    n = len(srcs)
+    arr = (_lib.WideSrc * max(n, 1))()
+    ramps, gains = (C.c_uint64 * (4 * max(n, 1)))(), (C.c_float * (2 * max(n, 1)))()
+    factors, fsteps = (C.c_void_p * max(n, 1))(), (C.c_uint64 * (3 * max(n, 1)))()
+    for k, s in enumerate(srcs):
+        arr[k].data = s.data if isinstance(s.data, int) or s.data is None else s.data.data_ptr()
+        arr[k].channels, arr[k].from_rate, arr[k].phase, arr[k].frames, arr[k].last, arr[k].gain = s.channels, s.from_rate, s.phase, s.frames, s.last, s.gain
+        ramps[4 * k], ramps[4 * k + 1], ramps[4 * k + 2], ramps[4 * k + 3] = s.kind, s.ramp_ns, s.first_frame, s.ramp_rate
+        gains[2 * k], gains[2 * k + 1] = s.start_gain, s.end_gain
+        t = s.factors
+        if t is None:
+            factors[k], entries = None, 0
+        elif isinstance(t, int):
+            if s.n_factors is None:
+                raise ValueError("player_mix_block: factors given as an address need their number of entries")
+            factors[k], entries = t, int(s.n_factors)
+        else:
+            torch = _t()
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError(f"player_mix_block: factors must be a contiguous float32 CUDA tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            factors[k], entries = t.data_ptr(), (t.numel() if s.n_factors is None else int(s.n_factors))
+        fsteps[3 * k], fsteps[3 * k + 1], fsteps[3 * k + 2] = s.factor_first, s.factor_period, entries
+    check(lib.rh_player_mix_block(C.c_void_p(dst) if isinstance(dst, int) else _ptr(dst), channels, to_rate, out_frames, arr, n, ramps, gains, factors, fsteps, _stream()),
+          "rh_player_mix_block")
+    return dst
+
+
 def wide_mix_batch(dsts, channels, to_rates, out_frames, srcs):
     """rh_wide_mix_batch: the current block of many mixers of any channel count in ONE launch; every mixer gets the bits rh_wide_mix_block
     writes for it.  dsts: per mixer a float32 device tensor of out_frames * channels elements, a device address, or None (out_frames == 0);
