@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 from conftest import knobs  # noqa: E402
+from dynamics_signals import limit_f64 as _limit_f64  # limit.rs:853-988 in float64: the ground truth of the ill-conditioned setting
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -145,28 +146,6 @@ def test_limiter_state_carried_across_blocks_equals_one_pass(G, O, ch):
     st0 = state[:1].clone()
     got_tail = G.limit_batch(torch.from_numpy(tail + 1e-3).cuda()[None, :], ch, 48000, state=st0).cpu().numpy()[0]
     assert float(np.max(np.abs(got_tail - ref_tail))) <= TOL
-
-
-def _limit_f64(x, ch, rate, threshold=-1.0, knee_width=4.0, attack_ns=5_000_000, release_ns=100_000_000):
-    """limit.rs:853-988 in float64 (the recurrences as vectorised-where-possible numpy; the coefficients rounded to f32 like
-    the reference's): the ground truth an ill-conditioned setting is measured against."""
-    from rodio_amd import _lib
-
-    att = float(_lib.lib.rh_duration_to_coefficient(attack_ns, rate))  # math.rs:110-113 in f32, as the kernels and the oracle get it
-    rel = float(_lib.lib.rh_duration_to_coefficient(release_ns, rate))
-    xv = x.astype(np.float64).reshape(-1, ch)
-    bias = np.log2(np.abs(xv) + 1.17549435e-38) * 0.30102999566398119521 * 20.0 - threshold
-    kb = bias * 2.0
-    g = np.where(kb < -knee_width, 0.0, np.where(np.abs(kb) <= knee_width, (kb + knee_width) ** 2 / (8.0 * knee_width), bias))
-    integ = np.zeros(ch)
-    peak = np.zeros(ch)
-    out = np.empty_like(xv)
-    for n in range(xv.shape[0]):
-        for c in range(ch):  # the channels' peaks are read as they stand when each sample is processed (limit.rs:946-960)
-            integ[c] = max(g[n, c], rel * integ[c] + (1.0 - rel) * g[n, c])
-            peak[c] = att * peak[c] + (1.0 - att) * integ[c]
-            out[n, c] = xv[n, c] * 2.0 ** (-peak.max() * 0.05 * 3.32192809488736234787)
-    return out.reshape(-1)
 
 
 @pytest.mark.parametrize("attack_ms,release_ms,tol", [(5, 100, TOL), (20, 1000, TOL), (800, 3000, None)])
