@@ -530,6 +530,67 @@ rh_status rh_player_mix_block(float *dst, uint32_t channels, uint32_t to_rate, u
                               const uint64_t *ramps_host, const float *ramp_gains_host,
                               const float *const *factors_dev_host, const uint64_t *factor_steps_host,
                               rh_stream stream);
+/* ---- A block of a mixer whose sources may be LOOPS: source.repeat_infinite() (src/source/mod.rs:204, repeat.rs:10-19) handed to Mixer::add
+ * or Player::append -- music, ambience, engines --, mixed from ONE resident pass of the sound.  dst receives out_frames frames of `channels`
+ * floats of the mix, in insertion order ((0 + v_0) + v_1) + ..., of
+ *     v_s = ChannelCountConverter(SampleRateConverter(Amplify(x_s)))
+ * A loop is not a modulo on the tap index.  Repeat sits on Buffered (repeat.rs:14), and UniformSourceIterator re-builds its converter chain
+ * from what the two report: extract() takes current_span_len().unwrap_or(32768) samples per span (buffered.rs:97-126);
+ * Buffered::current_span_len() is the span's WHOLE data.len(), not what is left of it (buffered.rs:207-214); Repeat never returns None, and
+ * once `inner` is exhausted it reports the parameters of `next`, the start of the sound (repeat.rs:37-44,58-64); every chain takes
+ * current_span_len().min(32768) samples (uniform.rs:56) and starts a fresh SampleRateConverter, whose last frame comes out verbatim
+ * (sample_rate.rs:193-200).  Two rules for where the chains cut follow:
+ *   rule 0  chains START OVER AT EVERY PASS.  A sound that answers None (decoders, TestSource): Buffered has spans of 32768 samples and a shorter
+ *           last one, and every chain is exactly one span; a sound of at most 32768 samples: one span, one chain per pass.  The last frame of
+ *           every chain, the pass's last frame included, is verbatim; the next pass starts a new converter at frame 0.
+ *   rule 1  chains RUN ON ACROSS THE SEAM.  A SamplesBuffer of more than 32768 samples answers Some(len) (buffer.rs:76-82): Buffered holds ONE
+ *           span of the whole sound and always reports len, so every chain is 32768 samples of the UNROLLED stream; the chain grid drifts
+ *           against the seam, and a chain that straddles it lerps from the sound's last frame to its first.
+ * A source is an rh_wide_src and RH_LOOP_WORDS 64-bit words of loops_host (a host array parallel to srcs_host, read before the call returns):
+ *   [0] loop_frames L   the frames of one pass.  0: NOT a loop -- the source is read exactly as rh_wide_mix_block reads it (phase, frames,
+ *                       last and all; the other words are ignored), so one music loop and twenty one-shots are one call, the ordered sum intact.
+ *   [1] chain_frames c  the input frames a converter chain takes: 1 <= c, c * src.channels <= 32768
+ *   [2] rule            0 or 1.  Rule 0: the last chain of a pass takes L mod c frames where that is not 0.  Rule 1 needs L >= c, so a chain
+ *                       crosses at most one seam (rodio produces it with L * ch > 32768 >= c * ch only).
+ *   [3] chain_start     the source frame (< L) at which the chain in progress at the block's first frame started; rule 0: a multiple of c
+ *   [4] chain_out       the output frames of that chain earlier blocks have emitted: less than the chain's output count,
+ *                       rh_uniform_span_frames(its input frames, from_rate, to_rate, 1, ..)
+ * Of a loop's rh_wide_src: data = frame 0 of the pass (L frames must be readable: every tap is taken inside them); channels, from_rate, gain
+ * as rh_wide_mix_block reads them; frames = the block's output frames the loop reaches -- it is silent behind them: a loop the caller stops
+ * there; phase and last are not read.  The cursor (words 3 and 4) is small however long the loop has been playing: no position of the
+ * kernel depends on the total play time.
+ * Bit-identical to the chain it replaces: with the gain in front, under rule 1 rh_uniform_row with span_len = c * channels over an unrolled
+ * copy, under rule 0 rh_uniform_row per pass, concatenated; then rh_wide_mix_block over the rows.  The same converter as everywhere: the lerp
+ * as mul, IEEE divide, add (math.rs:25), the verbatim last frame, F == T passes through (sample_rate.rs:133-136); channels.rs:57-85 behind
+ * it.  Rows need 4-byte alignment only.  A source with frames == 0 is not looked at; n_sources == 0 writes zeros; out_frames == 0 does
+ * nothing.  No host synchronisation and no allocation; one launch per 32 sources with frames > 0 (every source carries its own rates: no
+ * launch goes early), later launches continue from the stored partial sum.
+ * RH_ERR_INVALID, nothing written: what rh_wide_mix_block refuses of the shared fields (a loop's phase is not one); loops_host == NULL with
+ * n_sources > 0; a rule above 1; c == 0 or c * channels > 32768; rule 1 with L < c; a cursor outside its bounds (chain_start >= L, under
+ * rule 0 not a multiple of c, chain_out not below the chain's output count).
+ * RH_ERR_UNSUPPORTED, nothing written: F * T beyond 32 bits; out_frames > 0x7fffffff; a source that is not a loop with
+ * out_frames > (2^32 - 1 - T) / F (rh_player_mix_block's answer: refused, not cut); and a loop of which a position leaves 32 bits -- with
+ * M(n) = rh_uniform_span_frames(n, ..), EXACTLY one of:  L > 2^31;  M(c) * F > 2^32 - 1 (the positions j F of a chain's output frames);
+ * under rule 0  P = floor(L / c) * M(c) + M(L mod c) > 2^32 - 1  or  floor(chain_start / c) * M(c) + chain_out + frames - 1 > 2^32 - 1;
+ * under rule 1  chain_out + frames - 1 > 2^32 - 1  or  chain_start + floor((chain_out + frames - 1) / M(c)) * c > 2^32 - 1.  (44.1 -> 48 kHz,
+ * c = 16384: M(c) F = 2.6e6; no loop of audio rates comes near.)
+ *
+ * rh_loop_plan: the words of a sound of n_samples samples as rodio would play it, the cursor at 0.  span_len is what the sound handed to
+ * repeat_infinite() answers to current_span_len() while fresh: 0 = None -- n_samples <= 32768: c = L, rule 0; otherwise c = 32768 / channels,
+ * rule 0.  span_len == n_samples, the SamplesBuffer -- n_samples <= 32768: c = L, rule 0; otherwise c = 32768 / channels, rule 1.  Another
+ * constant span_len <= 32768 (decoder packets): c = min(span_len, n_samples) / channels, rule 0.  RH_ERR_UNSUPPORTED for anything that cuts a
+ * frame -- n_samples or the chain's samples not a multiple of channels: 3, 5, 6, 7 channels with a sound over 32768 samples; such a loop
+ * stays on the unrolled path, as rh_uniform_row plays cut frames -- and for a span_len above 32768 that is not n_samples.  Zero channels or
+ * samples, words == NULL: RH_ERR_INVALID.
+ * rh_loop_advance: the cursor behind a block of out_frames frames, in place.  ANY cut of a stream into blocks gives the bits of one pass.
+ * Words with L == 0 are left as they are.  It refuses what the entry refuses of the words.  Both are host arithmetic: no device, no
+ * rh_init needed. */
+enum { RH_LOOP_WORDS = 5 };
+rh_status rh_loop_plan(uint64_t n_samples, uint32_t channels, uint64_t span_len, uint64_t *words);
+rh_status rh_loop_advance(uint64_t *words, uint32_t from_rate, uint32_t to_rate, uint64_t out_frames);
+rh_status rh_loop_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
+                            const rh_wide_src *srcs_host, uint32_t n_sources,
+                            const uint64_t *loops_host, rh_stream stream);
 
 /* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
  * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays

@@ -743,6 +743,54 @@ def player_mix_block(dst, channels, to_rate, out_frames, srcs):
     return dst
 
 
+LOOP_WORDS = 5  # RH_LOOP_WORDS
+
+
+def loop_plan(n_samples, channels, span_len=0):
+    """rh_loop_plan: the words [loop_frames, chain_frames, rule, chain_start, chain_out] of a sound of n_samples samples handed to
+    repeat_infinite(), as rodio would play it; span_len = what the sound answers to current_span_len() while fresh (0: None;
+    n_samples: a SamplesBuffer).  The cursor starts at 0.  Host arithmetic: no device is touched."""
+    w = (C.c_uint64 * LOOP_WORDS)()
+    check(lib.rh_loop_plan(n_samples, channels, span_len, w), "rh_loop_plan")
+    return list(w)
+
+
+def loop_advance(words, from_rate, to_rate, out_frames):
+    """rh_loop_advance: the words of a loop behind a block of out_frames output frames (a new list; words of a plain source come back as
+    they are).  Any cut of a stream into blocks gives the bits of one pass."""
+    w = (C.c_uint64 * LOOP_WORDS)(*[int(v) for v in words])
+    check(lib.rh_loop_advance(w, from_rate, to_rate, out_frames), "rh_loop_advance")
+    return list(w)
+
+
+class LoopSrc:
+    """One source of loop_mix_block.  With words (loop_plan's, moved by loop_advance): a loop -- data is frame 0 of the resident pass (a float32
+    device tensor or a device address), frames the block's output frames it reaches; phase and last are not read.  Without: a source as
+    rh_wide_mix_block reads it."""
+
+    def __init__(self, data, channels, from_rate, frames, gain=1.0, words=None, phase=0, last=0xFFFFFFFF):
+        self.data, self.channels, self.from_rate, self.phase, self.frames, self.last, self.gain = data, int(channels), int(from_rate), int(phase), int(frames), int(last), float(gain)
+        self.words = [0] * LOOP_WORDS if words is None else [int(v) for v in words]
+        if len(self.words) != LOOP_WORDS:
+            raise ValueError(f"LoopSrc: a loop travels as {LOOP_WORDS} words, got {len(self.words)}")
+
+
+def loop_mix_block(dst, channels, to_rate, out_frames, srcs):
+    """rh_loop_mix_block: a block of a mixer whose sources may be loops (source.repeat_infinite()), each read from one resident pass: the
+    gain, the converter chain by chain as rodio cuts it, the channel rule and the ordered sum, one launch per 32 sources.  dst: a float32
+    device tensor of out_frames * channels elements (or a device address); srcs: LoopSrc objects in insertion order."""
+    _ensure()
+    n = len(srcs)
+    arr = (_lib.WideSrc * max(n, 1))()
+    words = (C.c_uint64 * (LOOP_WORDS * max(n, 1)))()
+    for k, s in enumerate(srcs):
+        arr[k].data = s.data if isinstance(s.data, int) or s.data is None else s.data.data_ptr()
+        arr[k].channels, arr[k].from_rate, arr[k].phase, arr[k].frames, arr[k].last, arr[k].gain = s.channels, s.from_rate, s.phase, s.frames, s.last, s.gain
+        words[LOOP_WORDS * k:LOOP_WORDS * (k + 1)] = s.words
+    check(lib.rh_loop_mix_block(C.c_void_p(dst) if isinstance(dst, int) else _ptr(dst), channels, to_rate, out_frames, arr, n, words, _stream()), "rh_loop_mix_block")
+    return dst
+
+
 def wide_mix_batch(dsts, channels, to_rates, out_frames, srcs):
     """rh_wide_mix_batch: the current block of many mixers of any channel count in ONE launch; every mixer gets the bits rh_wide_mix_block
     writes for it.  dsts: per mixer a float32 device tensor of out_frames * channels elements, a device address, or None (out_frames == 0);
