@@ -591,6 +591,74 @@ rh_status rh_loop_advance(uint64_t *words, uint32_t from_rate, uint32_t to_rate,
 rh_status rh_loop_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
                             const rh_wide_src *srcs_host, uint32_t n_sources,
                             const uint64_t *loops_host, rh_stream stream);
+/* ---- A block of a mixer whose sources may be QUEUES of sounds played back to back: what Player::append feeds its mixer (src/queue.rs,
+ * player.rs:104-108) -- a playlist, a sentence of word samples, an intro and a body --, every sound resident as a whole, each with a channel
+ * count, a rate and a gain of its own.  dst receives out_frames frames of `channels` floats of the mix, in insertion order
+ * ((0 + v_0) + v_1) + ..., of
+ *     v_s = ChannelCountConverter(SampleRateConverter(queue of Amplify(x_k)))
+ * THE CHAIN RULE.  A queue is not a concatenation of separately converted sounds.  UniformSourceIterator builds a converter chain from what
+ * the queue reports at the moment the previous chain runs dry: it takes current_span_len().min(32768) samples (uniform.rs:56) of channels()
+ * at sample_rate() (uniform.rs:58-67); the queue forwards the CURRENT sound's three answers (queue.rs:130-192: the next sound's as soon as
+ * the current one is exhausted); a SamplesBuffer answers its WHOLE length, not what is left of it (buffer.rs:76-82); and Take draws its
+ * samples from the QUEUE, whatever sounds they come from.  With the STREAM of a queue = the samples of its sounds back to back:
+ *   - a chain that starts at stream position p inside sound k takes min(samples_k, 32768) samples of the stream from p on and reads them as
+ *     frames of channels_k at rate_k.  A sound of at most 32768 samples that starts on a chain boundary is exactly one chain; a chain that
+ *     starts inside a longer sound runs on into the following sounds, reads THEIR samples in sound k's format (a mono sound's samples paired
+ *     up as stereo frames) and lerps across the seams.  The next chain starts where it ends, in the format of the sound it starts in.
+ *   - a chain ends early only where the sounds run out and the queue has no keep_alive: the queue has ENDED behind it (queue.rs:233-240).
+ *   - with keep_alive (every Player's queue) the samples the chain lacks are +0.0 (queue.rs:218-241; no gain multiplies them), the chain goes
+ *     on to its full count, and behind it the queue is live and SILENT: it adds +0.0 to every frame it reaches.
+ *   - inside a chain of n input frames the converter is the one used everywhere: output frame j (j restarts at 0 with every chain) reads
+ *     frames i = floor(j F / T) and i + 1 of the chain, a + (b - a) * num / T with the IEEE division (math.rs:25), the frame with i == n - 1
+ *     verbatim (sample_rate.rs:193-200), F == T passes through; n frames give rh_uniform_span_frames(n, from_rate, to_rate, 1, ..) output
+ *     frames.  channels.rs:57-85 applies behind it.  Each tap is x * gain of ITS sound, a rounded multiply of its own (amplify.rs:64).
+ * A sound is RH_QUEUE_SOUND_WORDS 64-bit words of sounds_host and one float of sound_gains_host (the layout of rh_player_mix_block's ramps: no
+ * struct is added): {data, samples, channels, rate} -- data: a device address, `samples` interleaved floats resident as a whole, 4-byte
+ * alignment is all it needs, may be 0 where samples == 0 (an empty sound is skipped); channels and rate as the sound reports them (behind
+ * `speed`, as rh_player_mix_block words it) -- and gain = the Amplify in FRONT of the queue (sound_gains_host == NULL: every gain is 1).
+ * A source is an rh_wide_src, sound_counts_host[s] sounds and RH_QUEUE_WORDS 64-bit words of cursors_host (host arrays, read before the
+ * call returns).  sounds_host and sound_gains_host hold the sounds of all sources back to back: source 0's, then source 1's.  A count of 0: NOT a queue -- the
+ * source is read exactly as rh_wide_mix_block reads it (phase, frames, last and all; its cursor words are ignored), so one music queue and
+ * twenty one-shots are one call, the ordered sum intact.  Of a queue's rh_wide_src only `frames` is read: the block's output frames the
+ * queue reaches -- it is silent behind them: a queue the caller stops there; format and gain travel per sound.  A source with frames == 0
+ * is not looked at.  The cursor of a queue, small however long it has played:
+ *   [0] chain_start  the sample offset into sounds[0] at which the chain in progress at the block's first frame STARTED: the caller lists a
+ *                    queue's sounds from that sound on and drops finished ones from the front.  Below sounds[0].samples (0 for an empty one).
+ *   [1] chain_out    the output frames of that chain earlier blocks have emitted: less than the chain's output count (at most
+ *                    rh_uniform_span_frames(32768 / channels, ..))
+ *   [2] state        0 playing, 1 silent (keep_alive, the sounds have run out), 2 ended.  In states 1 and 2 words 0 and 1 are 0, the
+ *                    sounds are not looked at and the source adds nothing.  (A count of 0 is a plain source: a queue whose sounds have all
+ *                    been dropped is left out of the call, or passed with frames == 0.)
+ *   [3] flags        bit 0: keep_alive
+ * rh_queue_plan: a fresh queue, the cursor at 0.  rh_queue_advance: the cursor behind a block of out_frames frames, in place, and in
+ * *dropped how many sounds the caller drops from the front before the next block (all of them once the state is 1 or 2).  ANY cut of a
+ * stream into blocks gives the bits of one pass.  Both are host arithmetic: no device, no rh_init needed.
+ * Bit-identical to the chain of entries it replaces: rh_amplify per sound into one concatenated row (zeros behind it for a keep_alive tail),
+ * rh_uniform_row per converter chain over its slice with the chain's format, the rows back to back, rh_wide_mix_block over the rows.
+ * n_sources == 0 writes zeros; out_frames == 0 does nothing.  On `stream`: one copy of the call's tables (from page-locked memory of the
+ * library's into the stream's scratch, as rh_wide_mix_batch does it) and ONE launch for any number of sources, sounds and seams.  A warmed
+ * call neither waits for the stream nor allocates (the first calls on a stream, and a call with larger tables than any before it, do; the
+ * fifth call in a row waits until the copy of the first has run).
+ * RH_ERR_INVALID, nothing written: what rh_wide_mix_block refuses of a plain source; dst NULL, channels or to_rate of 0; srcs_host or
+ * sound_counts_host NULL with n_sources > 0; sounds_host or cursors_host NULL where a queue reaches a frame; a queue with
+ * frames > out_frames; a sound with data 0 and samples > 0, or channels or rate of 0 or beyond 32 bits; a cursor outside its bounds (state > 2, flags > 1,
+ * chain_start not below sounds[0].samples unless both are 0, chain_out not below the chain's output count, words 0 / 1 not 0 in state 1 / 2).
+ * RH_ERR_UNSUPPORTED, nothing written: out_frames > 0x7fffffff; a plain source with out_frames > (2^32 - 1 - T) / F; and of a chain the
+ * block reaches: F * T beyond 32 bits; a sample count that is not a multiple of the chain's channel count (3, 5, 6 or 7 channels with a sound
+ * over 32768 samples; a seam chain that ends inside a frame, such as a stereo chain that ends with a mono sound of odd length) -- such a queue
+ * stays on the host path (SpanReader in rodio_hip.hpp), as rh_loop_plan words it; M * F > 2^32 - 1 with M the chain's output frames (the
+ * kernel computes j F in 32 bits; a chain has at most 32768 samples, so j F < 2^15 T + F: 44.1 -> 48 kHz stereo: 2.6e6).
+ * Out of scope: a sound appended to a queue that has already gone idle (queue.rs:136-146: its first frame is a chain of its own, one frame
+ * long -- the segment table of rh_queue_mix_plan.h can express it, the planner does not offer it yet); append_with_signal; try_seek;
+ * decoders that answer None, or spans shorter than the sound, as the sounds of a queue; GpuMixer planning such blocks in rodio_hip.hpp. */
+enum { RH_QUEUE_WORDS = 4, RH_QUEUE_SOUND_WORDS = 4 };
+rh_status rh_queue_plan(uint64_t *words, uint32_t keep_alive);
+rh_status rh_queue_advance(uint64_t *words, const uint64_t *sounds_host, uint32_t n_sounds,
+                           uint32_t to_rate, uint64_t out_frames, uint32_t *dropped);
+rh_status rh_queue_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
+                             const rh_wide_src *srcs_host, uint32_t n_sources,
+                             const uint64_t *sounds_host, const float *sound_gains_host,
+                             const uint32_t *sound_counts_host, const uint64_t *cursors_host, rh_stream stream);
 
 /* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
  * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays

@@ -145,6 +145,9 @@ SIGNATURES = {
     "rh_loop_plan": (i32, [u64, u32, u64, C.POINTER(u64)]),
     "rh_loop_advance": (i32, [C.POINTER(u64), u32, u32, u64]),
     "rh_loop_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(u64), vp]),
+    "rh_queue_plan": (i32, [C.POINTER(u64), u32]),
+    "rh_queue_advance": (i32, [C.POINTER(u64), C.POINTER(u64), u32, u32, u64, C.POINTER(u32)]),
+    "rh_queue_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(u64), f32p, C.POINTER(u32), C.POINTER(u64), vp]),
     "rh_mix_pair": (i32, [vp, vp, sz, vp, sz, vp]),
     "rh_uniform_row_out_samples": (i32, [u64, u32, u32, u32, u32, u64, C.POINTER(u64)]),
     "rh_uniform_row": (i32, [vp, u64, vp, u64, u32, u32, u32, u32, u64, C.POINTER(u64), vp]),

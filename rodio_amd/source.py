@@ -791,6 +791,87 @@ def loop_mix_block(dst, channels, to_rate, out_frames, srcs):
     return dst
 
 
+QUEUE_WORDS = 4  # RH_QUEUE_WORDS: chain_start, chain_out, state, flags
+QUEUE_SOUND_WORDS = 4  # RH_QUEUE_SOUND_WORDS: data, samples, channels, rate
+QUEUE_PLAYING, QUEUE_SILENT, QUEUE_ENDED = 0, 1, 2
+
+
+class QueueSound:
+    """One sound of a queue, resident as a whole: data (a float32 device tensor or a device address; None for an empty sound), samples
+    (the tensor's element count by default), channels and rate as the sound reports them, gain = the Amplify in front of the queue."""
+
+    def __init__(self, data, channels, rate, gain=1.0, samples=None):
+        if samples is None:
+            if data is None or isinstance(data, int):
+                raise ValueError("QueueSound: data given as an address needs its number of samples")
+            samples = data.numel()
+        self.data, self.samples, self.channels, self.rate, self.gain = data, int(samples), int(channels), int(rate), float(gain)
+
+    def address(self):
+        return 0 if self.data is None else (self.data if isinstance(self.data, int) else self.data.data_ptr())
+
+
+def _queue_sounds(sounds):
+    n = len(sounds)
+    words, gains = (C.c_uint64 * (QUEUE_SOUND_WORDS * max(n, 1)))(), (C.c_float * max(n, 1))()
+    for k, q in enumerate(sounds):
+        words[QUEUE_SOUND_WORDS * k:QUEUE_SOUND_WORDS * (k + 1)] = [q.address(), q.samples, q.channels, q.rate]
+        gains[k] = q.gain
+    return words, gains
+
+
+def queue_plan(keep_alive=True):
+    """rh_queue_plan: the cursor [chain_start, chain_out, state, flags] of a fresh queue (keep_alive: every Player's queue).  Host
+    arithmetic: no device is touched."""
+    w = (C.c_uint64 * QUEUE_WORDS)()
+    check(lib.rh_queue_plan(w, 1 if keep_alive else 0), "rh_queue_plan")
+    return list(w)
+
+
+def queue_advance(words, sounds, to_rate, out_frames):
+    """rh_queue_advance: (the cursor behind a block of out_frames output frames -- a new list --, how many of `sounds` the caller drops
+    from the front before the next block).  sounds: QueueSound objects from the one in which the chain in progress started.  Any cut of a
+    stream into blocks gives the bits of one pass."""
+    w = (C.c_uint64 * QUEUE_WORDS)(*[int(v) for v in words])
+    sw, _ = _queue_sounds(sounds)
+    dropped = C.c_uint32(0)
+    check(lib.rh_queue_advance(w, sw, len(sounds), to_rate, out_frames, C.byref(dropped)), "rh_queue_advance")
+    return list(w), dropped.value
+
+
+class QueueSrc:
+    """One source of queue_mix_block.  With sounds (QueueSound objects from the one in which the chain in progress started) and words
+    (queue_plan's, moved by queue_advance): a queue, frames the block's output frames it reaches.  Without: a source as rh_wide_mix_block
+    reads it (data, channels, from_rate, phase, last, gain)."""
+
+    def __init__(self, frames, sounds=None, words=None, data=None, channels=0, from_rate=0, gain=1.0, phase=0, last=0xFFFFFFFF):
+        self.data, self.channels, self.from_rate, self.phase, self.frames, self.last, self.gain = data, int(channels), int(from_rate), int(phase), int(frames), int(last), float(gain)
+        self.sounds = list(sounds or [])
+        self.words = [0] * QUEUE_WORDS if words is None else [int(v) for v in words]
+        if len(self.words) != QUEUE_WORDS:
+            raise ValueError(f"QueueSrc: a cursor travels as {QUEUE_WORDS} words, got {len(self.words)}")
+
+
+def queue_mix_block(dst, channels, to_rate, out_frames, srcs):
+    """rh_queue_mix_block: a block of a mixer whose sources may be queues of resident sounds played back to back (what Player::append
+    feeds its mixer): the converter chain by chain as rodio cuts it across the sounds, each tap behind its sound's gain, the channel rule
+    and the ordered sum, one launch for any number of sources.  dst: a float32 device tensor of out_frames * channels elements (or a
+    device address); srcs: QueueSrc objects in insertion order."""
+    _ensure()
+    n = len(srcs)
+    arr = (_lib.WideSrc * max(n, 1))()
+    counts, cursors = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * (QUEUE_WORDS * max(n, 1)))()
+    for k, s in enumerate(srcs):
+        arr[k].data = s.data if isinstance(s.data, int) or s.data is None else s.data.data_ptr()
+        arr[k].channels, arr[k].from_rate, arr[k].phase, arr[k].frames, arr[k].last, arr[k].gain = s.channels, s.from_rate, s.phase, s.frames, s.last, s.gain
+        counts[k] = len(s.sounds)
+        cursors[QUEUE_WORDS * k:QUEUE_WORDS * (k + 1)] = s.words
+    words, gains = _queue_sounds([q for s in srcs for q in s.sounds])
+    check(lib.rh_queue_mix_block(C.c_void_p(dst) if isinstance(dst, int) else _ptr(dst), channels, to_rate, out_frames, arr, n, words, gains, counts, cursors, _stream()),
+          "rh_queue_mix_block")
+    return dst
+
+
 def wide_mix_batch(dsts, channels, to_rates, out_frames, srcs):
     """rh_wide_mix_batch: the current block of many mixers of any channel count in ONE launch; every mixer gets the bits rh_wide_mix_block
     writes for it.  dsts: per mixer a float32 device tensor of out_frames * channels elements, a device address, or None (out_frames == 0);
