@@ -659,6 +659,84 @@ rh_status rh_queue_mix_block(float *dst, uint32_t channels, uint32_t to_rate, ui
                              const rh_wide_src *srcs_host, uint32_t n_sources,
                              const uint64_t *sounds_host, const float *sound_gains_host,
                              const uint32_t *sound_counts_host, const uint64_t *cursors_host, rh_stream stream);
+/* ---- A block of a mixer whose sources may be CLIPS ON A TIMELINE: a resident sound that starts after a delay, is cut to a duration and may
+ * fade out over that duration -- what sequencers, samplers, game schedulers and the "a" side of a crossfade add to a mixer:
+ *     mixer.add(sound.amplify(g).take_duration(len) [.set_filter_fadeout()] .delay(at))        (skip_duration(d) in front: the in-point)
+ * dst receives out_frames frames of `channels` floats of the mix, in insertion order ((0 + v_0) + v_1) + ..., of
+ *     v_s = ChannelCountConverter(SampleRateConverter(stream of the clip))
+ * THE STREAM.  With x a sound of n interleaved samples of ch channels at rate fr, all integers exact:
+ *   Z   = floor(delay_ns * ch * fr / 10^9) samples of +0.0 come first (delay.rs:8-16,68-75); Z need not be a multiple of ch.
+ *   dps = floor(10^9 / (fr * ch)) ns a sample; N = min(n, floor(take_ns / dps)) samples are admitted (take.rs:107-147); without a take N = n.
+ *   With the fade-out filter admitted sample k (counted over all channels) is (x_k * g) * R / Tt, R = float(floor((take_ns - k dps) / 10^6)),
+ *   Tt = float(floor(take_ns / 10^6)): two roundings, steps of one millisecond (take.rs:33-41); take_ns < 1 ms gives x * 0 / 0, as
+ *   rh_take_duration and rh_crossfade have it.  x_k * g is a rounded multiply of its own (amplify.rs:64); the zeros are not multiplied.
+ *   The stream is those Z + N samples, read as frames of ch samples BY STREAM POSITION: with Z mod ch != 0 a frame pairs samples across
+ *   the sound's own frames, from the first frame on, which straddles the zeros and the sound.
+ * THE CHAIN RULE.  UniformSourceIterator takes current_span_len().min(32768) samples per converter chain (uniform.rs:56); Delay adds its
+ * remaining zeros to the inner answer (delay.rs:94-98); TakeDuration ALWAYS answers Some(min(inner, remaining)) (take.rs:180-196); a
+ * SamplesBuffer answers its whole length (buffer.rs:76-82).
+ *   rule G  with a take, or a sound that answers Some(whole length): chains cut the stream at every multiple of 32768 samples from stream
+ *           position 0 -- the leading zeros are lerped into the sound's first frame, a grid line inside the sound ends a chain with a
+ *           verbatim frame --, the last chain takes what is left.
+ *   rule C  no take and a sound that answers None: the stream is one chain.
+ * Inside a chain of f frames the converter is the one used everywhere: output frame j reads frames i = floor(j F / T) and i + 1 of the
+ * chain, a + (b - a) * num / T with the IEEE division (math.rs:25), the frame with i == f - 1 verbatim (sample_rate.rs:193-200), F == T
+ * passes through; f frames give rh_uniform_span_frames(f, from_rate, to_rate, 1, ..) output frames; channels.rs:57-85 applies behind it.
+ * Behind its last chain the clip has ended.  (Where the duration expires inside a frame TakeDuration completes the frame with silence,
+ * take.rs:109-123; the last chain has taken its Z + N samples by then and that silence is never drawn.)
+ * A source is an rh_wide_src and RH_CLIP_WORDS 64-bit words of clips_host (a host array parallel to srcs_host, read before the call returns):
+ *   [0] kind      0: NOT a clip -- the source is read exactly as rh_wide_mix_block reads it (phase, frames, last and all; the other words are
+ *                 ignored), so scheduled clips and plain sources are one call, the ordered sum intact.  1: rule G.  2: rule C.
+ *   [1] Z   [2] N   [3] take_ns (0 without a take)   [4] flags: bit 0 a take is present, bit 1 the fade-out filter is set
+ *   [5] done      THE CURSOR: output frames of the clip that earlier blocks have emitted.  It is all the state there is: the chain in
+ *                 progress and the frame inside it (rule G), the first tap and its phase (rule C) follow from it on the host, in exact
+ *                 integer arithmetic, and the kernel sees positions counted from that chain's first sample only -- no position of the
+ *                 kernel depends on Z or on how long the clip has played.
+ *   [6] total     output frames of the whole clip at the rates of the last rh_clip_advance: `done == total` is the end.  rh_clip_plan does
+ *                 not know the mixer's rate and leaves 0; rh_clip_advance(words, .., 0) behind the plan states it.  The entry does not
+ *                 read this word (it works the count out itself).
+ * Of a clip's rh_wide_src: data = sample 0 of the sound, BEHIND the in-point (skip_duration(d) skips floor(d * fr / 10^9) * ch samples,
+ * skip.rs:62-71: the caller's offset into its buffer; a skipped SamplesBuffer goes on answering Some), N samples must be readable;
+ * channels, from_rate and gain as everywhere; frames = the block's output frames the clip reaches, at most total - done (frames of the
+ * delay count: they are frames of the clip); phase and last are not read.  A source with frames == 0 is not looked at.
+ * Bit-identical to the chain it replaces -- rh_amplify -> rh_take_duration (fade_out) -> rh_delay into one row of Z + N samples,
+ * rh_uniform_row over the row with span_len = the row's length under rule G and 0 under rule C, rh_wide_mix_block over the rows with gain
+ * 1 -- and to the reference's Mixer fed the adapter chains.  Rows need 4-byte alignment only.  n_sources == 0 writes zeros; out_frames == 0
+ * does nothing.  On `stream`: the table travels by value, 32 sources with frames > 0 a launch, later launches continue from the stored
+ * partial sum; the number of launches depends on the number of sources only, never on delays, takes or grid lines crossed.  No host
+ * synchronisation and no allocation.
+ * RH_ERR_INVALID, nothing written: what rh_wide_mix_block refuses of the shared fields (a clip's phase is not one); dst NULL, channels or
+ * to_rate of 0; srcs_host or clips_host NULL with n_sources > 0; words out of bounds: kind > 2, flags > 3, the fade-out without a take, rule C
+ * with a take, N above floor(take_ns / dps) with a take, done > total, a clip with frames > total - done.
+ * RH_ERR_UNSUPPORTED, nothing written: a chain that would end inside a frame -- (Z + N) mod ch != 0, or under rule G Z + N > 32768 with
+ * 32768 mod ch != 0 (3, 5, 6, 7 channels): such a clip stays on the row path, as rh_loop_plan words it; F * T beyond 32 bits;
+ * out_frames > 0x7fffffff; a plain source with out_frames > (2^32 - 1 - T) / F; Z, N or Z + N above 2^62, a total above 2^63, dps == 0 with a
+ * take (fr * ch > 10^9: rh_take_duration's answer); and what leaves 32 bits within ONE block -- with c = 32768 / ch where Z + N > 32768 under
+ * rule G and (Z + N) / ch otherwise, M = rh_uniform_span_frames(c, ..), EXACTLY one of:
+ *   rule G   M * F > 2^32 - 1;  j0 + frames - 1 > 2^32 - 1 with j0 = done mod M;
+ *            min((floor((j0 + frames - 1) / M) + 1) * c * ch, Z + N - floor(done / M) * c * ch) > 2^32 - 1   (the samples the block's chains span)
+ *   rule C   r0 + (frames - 1) * F > 2^32 - 1 with r0 = (done * F) mod T;
+ *            min((floor((r0 + (frames - 1) * F) / T) + 2) * ch, Z + N - floor(done * F / T) * ch) > 2^32 - 1
+ * A plain source is bounded as rh_wide_mix_block bounds it, by its positions phase + j F alone: its sample indices frame * channels may
+ * pass 2^32 (8 channels with F == T beyond 2^29 frames) and are formed in 64 bits, as that entry forms them.
+ * (44.1 -> 48 kHz stereo: M F = 2.6e6, and a block of 2^31 - 1 frames spans 3.9e9 samples: no block of audio comes near.)  The fade's
+ * millisecond index is 32-bit arithmetic per tap where (those samples) * dps + 999999 and the remaining milliseconds at the block's first
+ * chain fit 32 bits -- every block below 10^5 frames at audio rates --, 64-bit otherwise: slower, the same bits, never refused.
+ * rh_clip_plan: the words of a sound of n_samples samples behind the in-point, the cursor at 0.  span_len is what the sound answers to
+ * current_span_len(): 0 = None, a value >= n_samples = its whole length; anything between is RH_ERR_UNSUPPORTED (decoder packets cut
+ * chains elsewhere), and so is a clip that cuts a frame (above).  flags above 3, the fade-out without a take, zero channels or rate, words
+ * == NULL: RH_ERR_INVALID.  rh_clip_advance: the cursor behind a block of out_frames frames, in place (it stops at `total`), and word 6;
+ * `channels` and from_rate are the sound's.  ANY cut of a stream into blocks gives the bits of one pass.  Words of kind 0 are left as they
+ * are.  It refuses what the entry refuses of the words.  Both are host arithmetic: no device, no rh_init needed.
+ * Out of scope: GpuMixer planning such blocks in rodio_hip.hpp; constant decoder spans shorter than the sound; clips that cut a frame;
+ * fade_in, ramps and stepped volume on a clip (rh_player_mix_block has them); try_seek; loops or queues as clips. */
+enum { RH_CLIP_WORDS = 7 };
+rh_status rh_clip_plan(uint64_t *words, uint64_t n_samples, uint32_t channels, uint32_t rate, uint64_t span_len,
+                       uint64_t delay_ns, uint64_t take_ns, uint32_t flags);
+rh_status rh_clip_advance(uint64_t *words, uint32_t channels, uint32_t from_rate, uint32_t to_rate, uint64_t out_frames);
+rh_status rh_clip_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uint64_t out_frames,
+                            const rh_wide_src *srcs_host, uint32_t n_sources,
+                            const uint64_t *clips_host, rh_stream stream);
 
 /* ---- Mix, the two-input combinator: Source::mix(other) (src/source/mod.rs:255, src/source/mix.rs:10-22).  Mix::next (mix.rs:43-53) over two
  * rows that are already in the mix's format: dst[i] = a[i] + b[i] for i < min(na, nb) -- s1 + s2 with no leading zero, so -0.0 + -0.0 stays

@@ -142,6 +142,9 @@ SIGNATURES = {
     "rh_wide_mix_block_filtered": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(i32), f32p, C.POINTER(vp), i32, vp, u64, vp]),
     "rh_spatial_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(vp), C.POINTER(u64), vp]),
     "rh_player_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(u64), f32p, C.POINTER(vp), C.POINTER(u64), vp]),
+    "rh_clip_plan": (i32, [C.POINTER(u64), u64, u32, u32, u64, u64, u64, u32]),
+    "rh_clip_advance": (i32, [C.POINTER(u64), u32, u32, u32, u64]),
+    "rh_clip_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(u64), vp]),
     "rh_loop_plan": (i32, [u64, u32, u64, C.POINTER(u64)]),
     "rh_loop_advance": (i32, [C.POINTER(u64), u32, u32, u64]),
     "rh_loop_mix_block": (i32, [vp, u32, u32, u64, C.POINTER(WideSrc), u32, C.POINTER(u64), vp]),

@@ -19,7 +19,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "librodio_hip.so")
 # (the units that take longest to compile come first: the pool never starts a long pole last)
 SOURCES = ["rh_pipeline_wave.hip", "rh_limit.hip", "rh_pipeline_fast_hi.hip", "rh_pipeline_fast_lo.hip", "rh_pipeline_fast1.hip",
-           "rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_chunk.hip", "rh_pipeline_mix.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip", "rh_generators.hip", "rh_noise.hip", "rh_mix2.hip", "rh_spatialmix.hip", "rh_widebatch.hip", "rh_playermix.hip", "rh_loopmix.hip", "rh_queuemix.hip"]
+           "rh_runtime.hip", "rh_elementwise.hip", "rh_resample.hip", "rh_recurrence.hip", "rh_agc.hip", "rh_biquad_scan.hip", "rh_stream.hip", "rh_uniform.hip", "rh_widemix.hip", "rh_formats.hip", "rh_wav.hip", "rh_comm.hip", "rh_pipeline.hip", "rh_pipeline_chunk.hip", "rh_pipeline_mix.hip", "rh_pipeline_plan.hip", "rh_pipeline_stream.hip", "rh_pipeline_sblk.hip", "rh_live.hip", "rh_generators.hip", "rh_noise.hip", "rh_mix2.hip", "rh_spatialmix.hip", "rh_widebatch.hip", "rh_playermix.hip", "rh_loopmix.hip", "rh_queuemix.hip", "rh_clipmix.hip"]
 # -ffp-contract=off: the reference's f32 expressions (lerp, biquad, mixer sum) must not be
 # fused; kernels that want an FMA spell it __builtin_fmaf.
 # -fno-slp-vectorize: hipcc's SLP pass pairs the two stereo channels into v_pk_*_f32; on gfx950
@@ -94,6 +94,7 @@ DRIVERS = {
     "player_mix_plan_test": dict(hdrs=["rh_player_mix_plan.h"]),  # rh_player_mix_block: refusals, table sizes, the ramp that is a constant, launches and their kernel
     "loop_mix_plan_test": dict(hdrs=["rh_loop_mix_plan.h", "rh_player_mix_plan.h"]),  # rh_loop_mix_block: the two rules, the cursor, exact reciprocals, refusals, the 32-bit bound, launches
     "queue_mix_plan_test": dict(hdrs=["rh_queue_mix_plan.h", "rh_loop_mix_plan.h", "rh_player_mix_plan.h"]),  # rh_queue_mix_block: chains across sounds, the cursor, segments and pieces, refusals, the 32-bit bound
+    "clip_mix_plan_test": dict(hdrs=["rh_clip_mix_plan.h", "rh_loop_mix_plan.h", "rh_player_mix_plan.h"]),  # rh_clip_mix_block: the stream, the grid, the cursor, the fade's steps, refusals, the 32-bit bound
 }
 
 

@@ -872,6 +872,59 @@ def queue_mix_block(dst, channels, to_rate, out_frames, srcs):
     return dst
 
 
+CLIP_WORDS = 7  # RH_CLIP_WORDS: kind, Z, N, take_ns, flags, done, total
+CLIP_PLAIN, CLIP_RULE_G, CLIP_RULE_C = 0, 1, 2
+CLIP_TAKE, CLIP_FADE_OUT = 1, 2
+
+
+def clip_plan(n_samples, channels, rate, span_len=0, delay_ns=0, take_ns=None, fade_out=False):
+    """rh_clip_plan: the words [kind, Z, N, take_ns, flags, done, total] of sound.take_duration(take_ns)[.set_filter_fadeout()].delay(delay_ns)
+    over a sound of n_samples samples behind its in-point; span_len = what the sound answers to current_span_len() (0: None; n_samples: a
+    SamplesBuffer); take_ns None: no take.  The cursor starts at 0; `total` is clip_advance's to write.  Host arithmetic: no device is touched."""
+    w = (C.c_uint64 * CLIP_WORDS)()
+    flags = (CLIP_TAKE if take_ns is not None else 0) | (CLIP_FADE_OUT if fade_out else 0)
+    check(lib.rh_clip_plan(w, n_samples, channels, rate, span_len, delay_ns, take_ns or 0, flags), "rh_clip_plan")
+    return list(w)
+
+
+def clip_advance(words, channels, from_rate, to_rate, out_frames):
+    """rh_clip_advance: the words of a clip behind a block of out_frames output frames (a new list; the cursor stops at the clip's end, words
+    of a plain source come back as they are), with the clip's output frames at these rates in the last word: out_frames = 0 behind
+    clip_plan states them.  Any cut of a stream into blocks gives the bits of one pass."""
+    w = (C.c_uint64 * CLIP_WORDS)(*[int(v) for v in words])
+    check(lib.rh_clip_advance(w, channels, from_rate, to_rate, out_frames), "rh_clip_advance")
+    return list(w)
+
+
+class ClipSrc:
+    """One source of clip_mix_block.  With words (clip_plan's, moved by clip_advance): a clip -- data is sample 0 of the resident sound behind
+    its in-point (a float32 device tensor or a device address), frames the block's output frames it reaches; phase and last are not read.
+    Without: a source as rh_wide_mix_block reads it."""
+
+    def __init__(self, data, channels, from_rate, frames, gain=1.0, words=None, phase=0, last=0xFFFFFFFF):
+        self.data, self.channels, self.from_rate, self.phase, self.frames, self.last, self.gain = data, int(channels), int(from_rate), int(phase), int(frames), int(last), float(gain)
+        self.words = [0] * CLIP_WORDS if words is None else [int(v) for v in words]
+        if len(self.words) != CLIP_WORDS:
+            raise ValueError(f"ClipSrc: a clip travels as {CLIP_WORDS} words, got {len(self.words)}")
+
+
+def clip_mix_block(dst, channels, to_rate, out_frames, srcs):
+    """rh_clip_mix_block: a block of a mixer whose sources may be clips on a timeline (a resident sound behind delay, take_duration and its
+    fade-out): the delay's zeros, the gain, the fade, the converter chain by chain as rodio cuts the delayed stream, the channel rule and
+    the ordered sum, one launch per 32 sources.  dst: a float32 device tensor of out_frames * channels elements (or a device address);
+    srcs: ClipSrc objects in insertion order."""
+    _ensure()
+    n = len(srcs)
+    arr = (_lib.WideSrc * max(n, 1))()
+    words = (C.c_uint64 * (CLIP_WORDS * max(n, 1)))()
+    for k, s in enumerate(srcs):
+        arr[k].data = s.data if isinstance(s.data, int) or s.data is None else s.data.data_ptr()
+        arr[k].channels, arr[k].from_rate, arr[k].phase, arr[k].frames, arr[k].last, arr[k].gain = s.channels, s.from_rate, s.phase, s.frames, s.last, s.gain
+        words[CLIP_WORDS * k:CLIP_WORDS * (k + 1)] = s.words
+    check(lib.rh_clip_mix_block(C.c_void_p(dst) if isinstance(dst, int) else _ptr(dst), channels, to_rate, out_frames, arr, n, words, _stream()), "rh_clip_mix_block")
+    return dst
+
+
 def wide_mix_batch(dsts, channels, to_rates, out_frames, srcs):
     """rh_wide_mix_batch: the current block of many mixers of any channel count in ONE launch; every mixer gets the bits rh_wide_mix_block
     writes for it.  dsts: per mixer a float32 device tensor of out_frames * channels elements, a device address, or None (out_frames == 0);
