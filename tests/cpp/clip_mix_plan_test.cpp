@@ -5,6 +5,9 @@
 //     clip_mix_plan_test [seed [clips]]                      the whole run; prints its counters, exit status 1 on a failure
 //     clip_mix_plan_test plan n ch rate span_len delay_ns take_ns flags      -> status and the words
 //     clip_mix_plan_test advance w0 .. w6 ch from_rate to_rate out_frames    -> status and the words
+//     clip_mix_plan_test locate w0 .. w6 ch from_rate to_ch to_rate frames out_frames m ..
+//                          -> status, then "fade x0 M c klast zrel data-offset ms0" of describe(), then per output frame m of the block
+//                             "ia lerp num R": locate(), and the bits of fade_ms() of the first tap's channel 0 (0 where it meets none)
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -363,6 +366,27 @@ int main(int argc, char **argv) {
         std::printf("%d", (int)st);
         for (int k = 0; k < RH_CLIP_WORDS; ++k) std::printf(" %" PRIu64, w[k]);
         std::printf("\n");
+        return 0;
+    }
+    if (argc >= 2 && std::strcmp(argv[1], "locate") == 0 && argc >= 2 + RH_CLIP_WORDS + 6) {
+        uint64_t w[RH_CLIP_WORDS];
+        for (int k = 0; k < RH_CLIP_WORDS; ++k) w[k] = std::strtoull(argv[2 + k], nullptr, 10);
+        const char *const *a = argv + 2 + RH_CLIP_WORDS;
+        rh_wide_src x{};
+        x.data = kSound, x.channels = (uint32_t)std::strtoul(a[0], nullptr, 10), x.from_rate = (uint32_t)std::strtoul(a[1], nullptr, 10), x.frames = std::strtoull(a[4], nullptr, 10), x.gain = 1.0f;
+        Desc d;
+        const rh_status st = describe(x, w, (uint32_t)std::strtoul(a[2], nullptr, 10), (uint32_t)std::strtoul(a[3], nullptr, 10), std::strtoull(a[5], nullptr, 10), &d);
+        std::printf("%d\n", (int)st);
+        if (st != RH_OK) return 0;
+        std::printf("%u %u %u %u %u %u %" PRIu64 " %" PRIu64 "\n", d.fade, d.x0, d.M, d.c, d.klast, d.zrel, (uint64_t)(d.data - kSound), d.ms0);
+        for (int k = 2 + RH_CLIP_WORDS + 6; k < argc; ++k) {
+            const Taps t = locate(d, (uint32_t)std::strtoul(argv[k], nullptr, 10));
+            const uint64_t sa = tap_sample(d, t.ia, 0);
+            const float R = (d.fade != kNoFade && sa >= d.zrel) ? fade_ms(d, (uint32_t)(sa - d.zrel)) : 0.0f;
+            uint32_t rb;
+            std::memcpy(&rb, &R, 4);
+            std::printf("%u %d %u %u\n", t.ia, t.lerp ? 1 : 0, t.num, rb);
+        }
         return 0;
     }
     const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1;

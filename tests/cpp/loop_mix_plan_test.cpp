@@ -8,6 +8,8 @@
 //     loop_mix_plan_test [seed [random cases]]
 //     loop_mix_plan_test plan n_samples channels span_len              -> status L c rule chain_start chain_out
 //     loop_mix_plan_test advance L c rule start out from to out_frames -> status L c rule chain_start chain_out
+//     loop_mix_plan_test locate L c rule start out ch from to_ch to frames out_frames m ..
+//                          -> status, then "x0 P M" of describe(), then per output frame m of the block "ia ib lerp num" of locate()
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -390,6 +392,23 @@ int main(int argc, char **argv) {
         for (int k = 0; k < 5; ++k) w[k] = std::strtoull(argv[2 + k], nullptr, 10);
         const rh_status st = loop_advance(w, (uint32_t)std::strtoul(argv[7], nullptr, 10), (uint32_t)std::strtoul(argv[8], nullptr, 10), std::strtoull(argv[9], nullptr, 10));
         std::printf("%d %llu %llu %llu %llu %llu\n", (int)st, (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4]);
+        return 0;
+    }
+    if (argc >= 2 && std::strcmp(argv[1], "locate") == 0 && argc >= 13) {  // locate L c rule chain_start chain_out ch from_rate to_ch to_rate frames out_frames m ..
+        uint64_t w[5];
+        for (int k = 0; k < 5; ++k) w[k] = std::strtoull(argv[2 + k], nullptr, 10);
+        static float sound[8];  // an address that is never read through
+        rh_wide_src x{};
+        x.data = sound, x.channels = (uint32_t)std::strtoul(argv[7], nullptr, 10), x.from_rate = (uint32_t)std::strtoul(argv[8], nullptr, 10), x.frames = std::strtoull(argv[11], nullptr, 10), x.gain = 1.0f;
+        Desc d;
+        const rh_status st = describe(x, w, (uint32_t)std::strtoul(argv[9], nullptr, 10), (uint32_t)std::strtoul(argv[10], nullptr, 10), std::strtoull(argv[12], nullptr, 10), &d);
+        std::printf("%d\n", (int)st);
+        if (st != RH_OK) return 0;
+        std::printf("%u %u %u\n", d.x0, d.P, d.M);  // then per output frame m of the block: ia ib lerp num
+        for (int k = 13; k < argc; ++k) {
+            const Taps t = locate(d, (uint32_t)std::strtoul(argv[k], nullptr, 10));
+            std::printf("%u %u %d %u\n", t.ia, t.ib, t.lerp ? 1 : 0, t.num);
+        }
         return 0;
     }
     const uint64_t seed = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1;

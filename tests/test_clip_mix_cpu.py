@@ -192,6 +192,55 @@ def test_unequal_blocks_with_the_cursor_are_the_one_pass(case):
     assert same(np.concatenate(parts), whole)
 
 
+# ---- the windowed form: only the chains (rule G) or frames (rule C) a block touches ------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_the_windowed_form_is_the_whole_stream_one(case):
+    """clip_window() never builds the delay's zeros and walks no chain in front of the block.  The whole clip, and blocks at random cursors
+    -- one frame, one chain's end, anything --, against the form that was held against the oracle above."""
+    s = case.src()
+    whole = R.clip_whole(s, case.to_rate)
+    assert whole.shape[0] == s.frames == R.clip_out_frames_wide(s.words, case.ch, case.rate, case.to_rate)
+    if s.frames == 0:
+        return
+    assert same(R.clip_window(s, case.to_rate), whole)
+    assert same(R.clip_mix_window(case.to_ch, case.to_rate, s.frames + 3, [s]), R.clip_mix(case.to_ch, case.to_rate, s.frames + 3, [s]))
+    rng = np.random.default_rng(case.n + case.Z)
+    M = int(R.span_out(R.CHAIN_SAMPLES // case.ch, *R.reduced(case.rate, case.to_rate)))
+    cuts = [(int(d), int(n)) for d, n in zip(rng.integers(0, s.frames, 12), rng.integers(1, 700, 12))] + [(M - 1, 1), (M, 1), (M - 3, 7), (s.frames - 1, 1), (0, 1)]
+    for done, n in cuts:
+        if done < 0 or done >= s.frames:
+            continue
+        part = case.src(min(n, s.frames - done), done)
+        assert same(R.clip_window(part, case.to_rate), whole[done:done + part.frames]), (done, n)
+    # ... and the pure-int tap of single frames is the frame the stream form reads
+    S = R.stream(s.x, s.gain, s.words, case.ch, case.rate).reshape(-1, case.ch)
+    F, T = R.reduced(case.rate, case.to_rate)
+    for x in {0, s.frames - 1, s.frames // 2, min(M, s.frames - 1), min(M - 1, s.frames - 1)}:
+        ia, two, num = R.tap_of(s.words, case.ch, case.rate, case.to_rate, x)
+        with np.errstate(all="ignore"):
+            v = S[ia] + (S[ia + 1] - S[ia]) * np.float32(num) / np.float32(T) if two else S[ia]
+        assert same(v, whole[x]), x
+
+
+def test_the_windowed_form_with_the_rule_c_phase_at_a_large_done():
+    """Rule C keeps ONE converter: output frame `done + m` lies at (done + m) F of it, whatever done is.  65521 -> 65519 Hz, a delay of
+    200 002 samples and cursors up to the end: the phase done F mod T takes values all over [0, T), the whole-stream form still reaches."""
+    pair = WP.BY_ID["65521-65519"]
+    c = Case("rule C, a large phase", 60000, 200002, kind="test", rate=pair.from_rate, to_rate=pair.to_rate)
+    s = c.src()
+    whole = R.clip_whole(s, c.to_rate)
+    rng = np.random.default_rng(4)
+    phases = []
+    for done in [int(v) for v in rng.integers(90000, s.frames - 400, 10)] + [s.frames - 400, 99990]:
+        part = c.src(400, done)
+        assert same(R.clip_window(part, c.to_rate), whole[done:done + 400]), done
+        phases.append(done * pair.F % pair.T)
+        for m in (0, 399):
+            ia, two, num = R.tap_of(s.words, 2, c.rate, c.to_rate, done + m)
+            assert (ia, num) == ((done + m) * pair.F // pair.T, (done + m) * pair.F % pair.T)
+    assert max(phases) > pair.T * 3 // 4 and min(phases) < pair.T // 4
+
+
 # (n, ch, rate, span_len, Z, take, fade) the plan refuses
 REFUSED = [
     (40000, 2, 44100, 1152, 0, None, False, R.UNSUPPORTED),     # decoder packets
