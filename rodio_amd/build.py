@@ -90,11 +90,12 @@ DRIVERS = {
     "wide_filtered_test": dict(lib=True, fake=True),
     "rlm_launch_test": dict(hdrs=["rh_rlm_launch.h"]),  # the fused path's launch decisions: route, row cut, tickets, stream-block geometry
     "pcm16_launch_test": dict(hdrs=["rh_rlm_pcm16.h", "rh_rlm_launch.h"]),  # PCM16 sources: the rows themselves or a converted copy
-    "wide_batch_plan_test": dict(hdrs=["rh_wide_batch_plan.h"]),  # rh_wide_mix_batch: refusals, source ranges, and the tiles that cover every mixer's block once
-    "player_mix_plan_test": dict(hdrs=["rh_player_mix_plan.h"]),  # rh_player_mix_block: refusals, table sizes, the ramp that is a constant, launches and their kernel
-    "loop_mix_plan_test": dict(hdrs=["rh_loop_mix_plan.h", "rh_player_mix_plan.h"]),  # rh_loop_mix_block: the two rules, the cursor, exact reciprocals, refusals, the 32-bit bound, launches
-    "queue_mix_plan_test": dict(hdrs=["rh_queue_mix_plan.h", "rh_loop_mix_plan.h", "rh_player_mix_plan.h"]),  # rh_queue_mix_block: chains across sounds, the cursor, segments and pieces, refusals, the 32-bit bound
-    "clip_mix_plan_test": dict(hdrs=["rh_clip_mix_plan.h", "rh_loop_mix_plan.h", "rh_player_mix_plan.h"]),  # rh_clip_mix_block: the stream, the grid, the cursor, the fade's steps, refusals, the 32-bit bound
+    "wide_batch_plan_test": dict(hdrs=["rh_wide_batch_plan.h", "rh_mix_plan.h"]),  # rh_wide_mix_batch: refusals, source ranges, and the tiles that cover every mixer's block once
+    "player_mix_plan_test": dict(hdrs=["rh_player_mix_plan.h", "rh_mix_plan.h"]),  # rh_player_mix_block: refusals, table sizes, the ramp that is a constant, launches and their kernel
+    "loop_mix_plan_test": dict(hdrs=["rh_loop_mix_plan.h", "rh_mix_plan.h"]),  # rh_loop_mix_block: the two rules, the cursor, exact reciprocals, refusals, the 32-bit bound, launches
+    "queue_mix_plan_test": dict(hdrs=["rh_queue_mix_plan.h", "rh_mix_plan.h"]),  # rh_queue_mix_block: chains across sounds, the cursor, segments and pieces, refusals, the 32-bit bound
+    "mix_plan_test": dict(hdrs=["rh_mix_plan.h"]),  # what the block mixers share: the source rule, the step index, the slots and launches, the alike cut
+    "clip_mix_plan_test": dict(hdrs=["rh_clip_mix_plan.h", "rh_mix_plan.h"]),  # rh_clip_mix_block: the stream, the grid, the cursor, the fade's steps, refusals, the 32-bit bound
 }
 
 

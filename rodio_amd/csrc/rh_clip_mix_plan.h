@@ -15,24 +15,25 @@
 // do, and the kernel sees positions counted from that chain's (that tap's) first sample only.
 #pragma once
 #include <cstdint>
-#include <numeric>
 
 #include "../../include/rodio_hip.h"
-#include "rh_loop_mix_plan.h"
+#include "rh_mix_plan.h"
 
 namespace rh {
 namespace clipmix {
 
-namespace lm = rh::loopmix;
+namespace lm = rh::mixplan;  // the rules the block mixers share
 using lm::Div;
 using lm::div_u32;
+using lm::kChainSamples;
+using lm::kChunk;  // sources a launch
 using lm::kDivZero;
+using lm::kGroup;  // ... walked in groups of this many
+using lm::Launch;  // every source brings its own positions: a launch is full at kChunk sources and for no other reason
 using lm::make_div;
+using lm::walk;
 typedef unsigned __int128 u128;
 
-constexpr uint32_t kChunk = lm::kChunk;  // sources a launch (the table travels by value in the kernel-argument segment)
-constexpr uint32_t kGroup = lm::kGroup;  // ... walked in groups of this many
-constexpr uint64_t kChainSamples = lm::kChainSamples;
 constexpr uint64_t kMaxStream = 1ull << 62;  // Z, N and Z + N stay below this: every sum below fits 64 bits
 constexpr uint64_t kNsPerMs = 1000000ull;
 // floor(x / 10^6) for every x < 2^32 (lm::make_div(10^6), spelled out so that the kernel holds it as two literals)
@@ -131,8 +132,9 @@ struct Rates {
 };
 inline rh_status rates_of(uint32_t from_rate, uint32_t to_rate, Rates *r) {
     if (from_rate == 0 || to_rate == 0) return RH_ERR_INVALID;
-    const uint32_t g = std::gcd(from_rate, to_rate);
-    r->F = from_rate / g, r->T = to_rate / g;
+    uint32_t F, T;
+    lm::reduce(from_rate, to_rate, &F, &T);
+    r->F = F, r->T = T;
     return r->F * r->T > 0xffffffffull ? RH_ERR_UNSUPPORTED : RH_OK;  // the reference multiplies in u32 (sample_rate.rs:157,173)
 }
 
@@ -184,7 +186,7 @@ struct Taps {
     uint32_t num;  // (position) mod T: the lerp's weight over T
 };
 // Output frame m of the block.  Every intermediate fits 32 bits for a call check() has passed.
-RH_LOOP_HD Taps locate(const Desc &d, uint32_t m) {
+RH_MIX_HD Taps locate(const Desc &d, uint32_t m) {
     const uint32_t x = d.x0 + m;
     const uint32_t k = div_u32(x, d.dM), j = x - k * d.M;  // the chain and the frame inside it
     const uint32_t pos = d.r0 + j * d.F;
@@ -198,10 +200,10 @@ RH_LOOP_HD Taps locate(const Desc &d, uint32_t m) {
 // The stream sample of channel k of frame ia, counted from the descriptor's origin.  64 bits: a clip's stays below 2^32 (describe() refuses
 // the block otherwise), a plain source's need not -- rh_wide_mix_block bounds its positions phase + j F, not frame * channels, and a plain
 // source is read as that entry reads it.
-RH_LOOP_HD uint64_t tap_sample(const Desc &d, uint32_t ia, uint32_t k) { return (uint64_t)ia * d.ch + k; }
+RH_MIX_HD uint64_t tap_sample(const Desc &d, uint32_t ia, uint32_t k) { return (uint64_t)ia * d.ch + k; }
 // take.rs:33-41 for the sound's sample data[krel]: float(floor(remaining / 10^6)), remaining = ms0 10^6 + (999999 - ns_pad) - krel dps, which is
 // ms0 - floor((krel dps + ns_pad) / 10^6): 0 <= ns_pad <= 999999, so the numerator is never negative.  kFade32: it and ms0 fit 32 bits.
-RH_LOOP_HD float fade_ms(const Desc &d, uint32_t krel) {
+RH_MIX_HD float fade_ms(const Desc &d, uint32_t krel) {
     if (d.fade == kFade32) return (float)((uint32_t)d.ms0 - div_u32(krel * d.dps + d.ns_pad, kDivMs));
     return (float)(d.ms0 - ((uint64_t)krel * d.dps + d.ns_pad) / kNsPerMs);
 }
@@ -210,19 +212,22 @@ RH_LOOP_HD float fade_ms(const Desc &d, uint32_t krel) {
 inline rh_status describe(const rh_wide_src &x, const uint64_t *words, uint32_t channels, uint32_t to_rate, uint64_t out_frames, Desc *out) {
     const Words w = words_of(words);
     Desc d{};
-    if (w.kind == kPlain) {  // rh_wide_mix_block's source (rh_player_mix_plan.h holds its answers)
-        playermix::Reach r;
-        const rh_status st = playermix::check_src(x, channels, to_rate, out_frames, &r);
+    if (w.kind == kPlain) {  // rh_wide_mix_block's source
+        lm::Reach r;
+        const rh_status st = lm::check_src(x, channels, to_rate, out_frames, &r);
         if (st != RH_OK) return st;
         d.data = x.data, d.ch = x.channels, d.frames = (uint32_t)x.frames, d.gain = x.gain, d.Tf = r.F == r.T ? 0.0f : (float)r.T, d.F = r.F, d.T = r.T, d.r0 = x.phase;
         d.klast = 0u, d.nl = d.nl_last = x.last, d.dM = kDivZero, d.dT = make_div(r.T);
         *out = d;
         return RH_OK;
     }
-    if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-    Rates r;
-    rh_status st = rates_of(x.from_rate, to_rate, &r);
+    rh_wide_src y = x;
+    y.phase = 0;  // (a clip's positions come from its words: the field is not read)
+    uint32_t F32, T32;
+    uint64_t fit;
+    rh_status st = lm::check_src(y, to_rate, out_frames, &F32, &T32, &fit);
     if (st != RH_OK) return st;
+    const Rates r{F32, T32};
     Shape s;
     st = shape_of(w, x.channels, x.from_rate, r.F, r.T, &s);
     if (st != RH_OK) return st;
@@ -281,9 +286,6 @@ inline rh_status check(const float *dst, uint32_t channels, uint32_t to_rate, ui
     }
     return RH_OK;
 }
-
-using lm::Launch;
-using lm::walk;
 
 }  // namespace clipmix
 }  // namespace rh

@@ -23,10 +23,12 @@
 // (32 sources a launch; more continue from the stored partial sum).
 #include "rh_common.h"
 #include "rh_clip_mix_plan.h"
+#include "rh_mix_dev.h"
 
 namespace {
 
 namespace cm = rh::clipmix;
+namespace md = rh::mixdev;
 
 constexpr int kBlock = 256;
 constexpr int kGroup = (int)cm::kGroup;
@@ -40,18 +42,7 @@ template <bool CONT>
 __global__ __launch_bounds__(kBlock) void k_clip_mix(float *__restrict__ dst, uint32_t to_ch, uint32_t out_frames, const ClipTable tbl, uint32_t n_sources) {
     const uint64_t total = (uint64_t)out_frames * to_ch;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    {
-        // (k_wide_mix: the table is read through the scalar cache, and the first wave of a CU would miss on its lines one after the
-        //  other.  One word of every line is asked for here, all requests in flight at once.)
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(&tbl);
-        constexpr uint32_t kLines = (sizeof(ClipTable) + 63) / 64;
-        uint32_t t[kLines], touch = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) t[q] = w[q * 16u];
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) touch |= t[q];
-        asm volatile("" ::"s"(touch));
-    }
+    md::touch_table(tbl);  // (the first wave of a CU would miss on the table's lines one after the other)
     for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < total; o += stride) {
         const uint32_t m = (uint32_t)(o / to_ch);
         const uint32_t c = (uint32_t)(o - (uint64_t)m * to_ch);
@@ -65,8 +56,8 @@ __global__ __launch_bounds__(kBlock) void k_clip_mix(float *__restrict__ dst, ui
                 const cm::Desc &d = tbl.d[s0 + u];
                 const cm::Taps t = cm::locate(d, m);
                 wv[u] = (float)t.num;  // math.rs:25 multiplies by it, then divides by T
-                const uint32_t k = c < d.ch ? c : 0u;                          // channels.rs:59-70: k < from: the input channel; k == 1 of a mono source: its only one;
-                on[u] = m < d.frames && (c < d.ch || (c == 1u && d.ch == 1u));  // otherwise 0.0
+                const uint32_t k = md::in_channel(c, d.ch);
+                on[u] = m < d.frames && md::has_channel(c, d.ch);
                 lerp[u] = on[u] && t.lerp;
                 const uint64_t sa = cm::tap_sample(d, t.ia, k), sb = sa + d.ch;  // stream samples, counted from the chain in progress
                 ra[u] = on[u] && sa >= d.zrel;                       // in front of zrel: the delay's +0.0, nothing is loaded

@@ -90,6 +90,13 @@ hipError_t counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uin
 // ScratchAux (rh_scan_launch.h): what the last user of a stream's scratch left behind, for a user that can save itself work when IT was the
 // last one.  Zeroed when the buffer is (re)allocated and by every call that does not ask for it.  Read and written under `hold`.
 hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, std::unique_lock<std::mutex> &hold, ScratchAux **aux = nullptr);
+// A host table's way into the stream's scratch: page-locked buffers owned by the library, a ring of four per stream, each rewritten only
+// after an event recorded behind the copy that read it has fired (the rule of the fused pipeline's descriptor ring, rh_pipeline_internal.h).
+// Under `hold` of stream_scratch: table_stage waits for the ring's next buffer, grows it to `bytes` and hands it out; the caller writes its
+// tables there; table_send queues the copy of those `bytes` to `dev` and records the event (hipErrorInvalidValue where nothing is staged on
+// the stream).  The ring goes with the stream's scratch.
+hipError_t table_stage(hipStream_t s, size_t bytes, char **host);
+hipError_t table_send(hipStream_t s, void *dev);
 // device-to-device copy as a launch on `hs` (hipMemcpyAsync DeviceToDevice makes the calling thread wait for the queue ahead of it)
 hipError_t copy_d2d(void *dst, const void *src, size_t bytes, hipStream_t hs);
 // The lerp's division `(b - a) * num / T` (math.rs:25) in three instructions instead of the IEEE sequence's ten -- q0 = t * r, rem = fma(-q0, T, t),

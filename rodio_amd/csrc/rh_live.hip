@@ -10,6 +10,7 @@
 #include <mutex>
 
 #include "rh_common.h"
+#include "rh_mix_plan.h"
 
 namespace {
 
@@ -18,33 +19,11 @@ constexpr int kBlock = 256;
 // first sample inside its period, then fits in 32 bits.
 constexpr uint64_t kMaxLaunchSamples = 1ull << 30;
 
-// x / d for x < 2^32, 1 <= d <= 2^31 (the round-up method, Granlund-Montgomery): m = floor(2^32 (2^l - d) / d) + 1, l = ceil(log2 d);
-// q = (hi(x m) + ((x - hi(x m)) >> min(l, 1))) >> max(l - 1, 0).  Exact for every x (tests/test_gpu_live.py checks the boundaries).
-struct StepDiv {
-    uint32_t phase;  // (first % period), reduced as below
-    uint32_t m, s1, s2;
-    __device__ __forceinline__ uint32_t step(uint32_t i) const {
-        const uint32_t x = phase + i;
-        const uint32_t t = __umulhi(x, m);
-        return (t + ((x - t) >> s1)) >> s2;
-    }
-};
-
-// The table index of sample i (< n <= 2^30) of a block whose first sample is the stream's sample `first`, for `period` >= 1.
-StepDiv step_div(uint64_t first, uint64_t period, uint64_t n) {
-    uint64_t d = period, phase = first % period;
-    if (d > (1ull << 31)) {
-        // at most one boundary inside the block, at i = period - phase: the same quotient with d = 2^31 and the phase moved so that the
-        // boundary stays where it is (i < 2^30 keeps phase + i below 2^32)
-        const uint64_t t = d - phase;
-        d = 1ull << 31;
-        phase = t >= n ? 0 : d - t;
-    }
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-    return StepDiv{(uint32_t)phase, (uint32_t)m, l < 1 ? l : 1u, l > 1 ? l - 1 : 0u};
-}
+// The step index (rh_mix_plan.h): x / d for x < 2^32, 1 <= d <= 2^31 by the round-up method (Granlund-Montgomery), exact for every x
+// (tests/test_gpu_live.py checks the boundaries), and the table index of sample i (< n <= 2^30) of a block whose first sample is the
+// stream's sample `first`: step_div(first, period, n).
+using rh::mixplan::StepDiv;
+using rh::mixplan::step_div;
 
 // Entries of a table that covers samples [first, first + n) at `period`.
 uint64_t steps_needed(uint64_t first, uint64_t period, uint64_t n) { return n ? (first + n - 1) / period - first / period + 1 : 0; }

@@ -14,49 +14,25 @@
 //           taps are taken mod L.
 #pragma once
 #include <cstdint>
-#include <numeric>
 
 #include "../../include/rodio_hip.h"
-#include "rh_player_mix_plan.h"
-
-#if defined(__HIPCC__)
-#define RH_LOOP_HD __host__ __device__ __forceinline__
-#else
-#define RH_LOOP_HD inline
-#endif
+#include "rh_mix_plan.h"
 
 namespace rh {
 namespace loopmix {
 
-constexpr uint32_t kChunk = 32;               // sources a launch (the table travels by value in the kernel-argument segment)
-constexpr uint32_t kGroup = 4;                // ... walked in groups of this many: a launch's slots are whole groups
-constexpr uint64_t kChainSamples = 32768;     // uniform.rs:56: what a converter chain takes at most
+using mixplan::Div;
+using mixplan::div_u32;
+using mixplan::kChainSamples;
+using mixplan::kChunk;  // sources a launch
+using mixplan::kDivZero;
+using mixplan::kGroup;  // ... walked in groups of this many: a launch's slots are whole groups
+using mixplan::Launch;  // every source brings its own positions: a launch is full at kChunk sources and for no other reason
+using mixplan::make_div;
+using mixplan::span_out;
+using mixplan::walk;
+
 constexpr uint64_t kMaxLoopFrames = 1ull << 31;  // base + i + 1 < 2 L stays inside 32 bits
-
-// x / d for every x < 2^32 and 1 <= d < 2^32 without a division (the round-up method: m = floor(2^32 (2^l - d) / d) + 1 with
-// l = ceil(log2 d); q = (t + ((x - t) >> min(l, 1))) >> max(l - 1, 0) with t = the high word of x m).  sh = s1 | s2 << 8.
-struct Div {
-    uint32_t m, sh;
-};
-RH_LOOP_HD uint32_t div_u32(uint32_t x, Div d) {
-    const uint32_t t = (uint32_t)(((uint64_t)x * d.m) >> 32);
-    return (t + ((x - t) >> (d.sh & 0xffu))) >> (d.sh >> 8);
-}
-inline Div make_div(uint64_t d) {
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-    return Div{(uint32_t)m, (l < 1 ? l : 1u) | ((l > 1 ? l - 1 : 0u) << 8)};
-}
-constexpr Div kDivZero = Div{0u, 31u | (31u << 8)};  // the quotient 0 for every x: a position a source does not have
-
-// Output frames of a complete chain of n input frames: rh_uniform_span_frames(n, F, T, 1, ..) for reduced F / T (n <= 2^31, T < 2^32).
-inline uint64_t span_out(uint64_t n, uint64_t F, uint64_t T) {
-    if (F == T || n == 0) return n;
-    uint64_t c = ((n - 1) * T + F - 1) / F;  // the frames with floor(j F / T) <= n - 2
-    if (c * F < n * T) c += 1;               // ... and the one that lands on the last frame, where one does
-    return c;
-}
 
 // The words of a source.
 struct Words {
@@ -110,9 +86,9 @@ inline rh_status loop_advance(uint64_t *words, uint32_t from_rate, uint32_t to_r
     if (!words || from_rate == 0 || to_rate == 0) return RH_ERR_INVALID;
     Words w = words_of(words);
     if (w.L == 0) return RH_OK;  // not a loop: data and phase move, as for rh_wide_mix_block
-    const uint32_t g = std::gcd(from_rate, to_rate);
-    const uint64_t F = from_rate / g, T = to_rate / g;
-    if (F * T > 0xffffffffull) return RH_ERR_UNSUPPORTED;
+    uint32_t F, T;
+    mixplan::reduce(from_rate, to_rate, &F, &T);
+    if ((uint64_t)F * T > 0xffffffffull) return RH_ERR_UNSUPPORTED;
     // (the channel count only bounds c: 1 admits every chain the entry can take)
     uint64_t M, P;
     const rh_status st = check_words(w, 1, F, T, &M, &P);
@@ -157,7 +133,7 @@ struct Taps {
     uint32_t num;     // (position) mod T: the lerp's weight over T
 };
 // Output frame m of the block.  Every intermediate fits 32 bits for a call check() has passed.
-RH_LOOP_HD Taps locate(const Desc &d, uint32_t m) {
+RH_MIX_HD Taps locate(const Desc &d, uint32_t m) {
     const uint32_t x = d.x0 + m;
     const uint32_t p = x - div_u32(x, d.dP) * d.P;           // rule 0: inside the pass
     const uint32_t k = div_u32(p, d.dM), j = p - k * d.M;    // the chain and the frame inside it
@@ -179,28 +155,29 @@ RH_LOOP_HD Taps locate(const Desc &d, uint32_t m) {
 inline rh_status describe(const rh_wide_src &x, const uint64_t *words, uint32_t channels, uint32_t to_rate, uint64_t out_frames, Desc *out) {
     const Words w = words_of(words);
     Desc d{};
-    if (w.L == 0) {  // rh_wide_mix_block's source (rh_player_mix_plan.h holds its answers)
-        playermix::Reach r;
-        const rh_status st = playermix::check_src(x, channels, to_rate, out_frames, &r);
+    if (w.L == 0) {  // rh_wide_mix_block's source
+        mixplan::Reach r;
+        const rh_status st = mixplan::check_src(x, channels, to_rate, out_frames, &r);
         if (st != RH_OK) return st;
         d = Desc{x.data, x.channels, (uint32_t)x.frames, x.gain, r.F == r.T ? 0.0f : (float)r.T, r.F, r.T, x.phase, 0u, 0u, 0u, 0u, 0u, 0xffffffffu, 0xffffffffu, x.last, x.last,
                  kDivZero, kDivZero, kDivZero, make_div(r.T)};
         *out = d;
         return RH_OK;
     }
-    if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-    const uint32_t g = std::gcd(x.from_rate, to_rate);
-    const uint64_t F = x.from_rate / g, T = to_rate / g;
-    if (F * T > 0xffffffffull) return RH_ERR_UNSUPPORTED;  // the reference multiplies in u32 (sample_rate.rs:157,173)
-    uint64_t M, P;
-    const rh_status st = check_words(w, x.channels, F, T, &M, &P);
+    rh_wide_src y = x;
+    y.phase = 0;  // (a loop's positions come from its words: the field is not read)
+    uint32_t F, T;
+    uint64_t fit, M, P;
+    rh_status st = mixplan::check_src(y, to_rate, out_frames, &F, &T, &fit);
+    if (st != RH_OK) return st;
+    st = check_words(w, x.channels, F, T, &M, &P);
     if (st != RH_OK) return st;
     const uint64_t x0 = w.rule == 0 ? (w.chain_start / w.c) * M + w.chain_out : w.chain_out;
     const uint64_t x_last = x0 + x.frames - 1;
     if (x_last > 0xffffffffull) return RH_ERR_UNSUPPORTED;
     if (w.rule == 1 && w.chain_start + (x_last / M) * w.c > 0xffffffffull) return RH_ERR_UNSUPPORTED;
     const uint64_t tail = w.L % w.c;
-    d = Desc{x.data, x.channels, (uint32_t)x.frames, x.gain, F == T ? 0.0f : (float)T, (uint32_t)F, (uint32_t)T, 0u, (uint32_t)x0, (uint32_t)P, (uint32_t)M, (uint32_t)w.c,
+    d = Desc{x.data, x.channels, (uint32_t)x.frames, x.gain, F == T ? 0.0f : (float)T, F, T, 0u, (uint32_t)x0, (uint32_t)P, (uint32_t)M, (uint32_t)w.c,
              w.rule == 1 ? (uint32_t)w.chain_start : 0u, (uint32_t)w.L, w.rule == 0 ? (uint32_t)(w.L / w.c) : 0xffffffffu, (uint32_t)w.c - 1u, (uint32_t)(tail ? tail : w.c) - 1u,
              w.rule == 0 ? make_div(P) : kDivZero, make_div(M), w.rule == 1 ? make_div(w.L) : kDivZero, make_div(T)};
     *out = d;
@@ -222,29 +199,6 @@ inline rh_status check(const float *dst, uint32_t channels, uint32_t to_rate, ui
         if (st != RH_OK) return st;
     }
     return RH_OK;
-}
-
-// One launch: up to kChunk sources in insertion order.
-struct Launch {
-    uint32_t n;            // sources (0: no source reaches the block, the launch writes zeros)
-    uint32_t src[kChunk];  // their indices in the caller's table
-    bool cont;             // it continues from the partial sum an earlier launch of the call stored
-};
-// The launches of a call, in order: emit(const Launch &) for each.  Every source brings its own positions, so a launch is full at kChunk
-// sources and for no other reason.
-template <class Emit>
-inline void walk(const rh_wide_src *srcs, uint32_t n_sources, Emit &&emit) {
-    Launch L;
-    L.n = 0, L.cont = false;
-    for (uint32_t s = 0; s < n_sources; ++s) {
-        if (srcs[s].frames == 0) continue;
-        L.src[L.n] = s;
-        if (++L.n == kChunk) {
-            emit(static_cast<const Launch &>(L));
-            L.n = 0, L.cont = true;
-        }
-    }
-    if (L.n || !L.cont) emit(static_cast<const Launch &>(L));
 }
 
 }  // namespace loopmix

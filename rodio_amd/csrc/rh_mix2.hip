@@ -12,8 +12,8 @@
 //                    of pairs in ONE launch (k_crossfade); pairs the kernel does not take run through the stand-alone calls instead
 // The arithmetic of the fused kernel is rh_rows_dev.h's, which the stand-alone kernels call as well.
 #include <algorithm>
+#include <cstring>
 #include <numeric>
-#include <unordered_map>
 #include <vector>
 
 #include "rh_common.h"
@@ -253,45 +253,6 @@ bool cf_fused_ok(const CfPair &p, const CfShape &s, CfPlan *g, uint64_t duration
     return true;
 }
 
-// The plan table's way to the device: page-locked tables, a ring of them per stream, each rewritten only after an event recorded behind
-// the copy that read it has fired (the rule of the fused pipeline's descriptor ring, rh_pipeline_internal.h).  Used under the
-// stream's scratch lock.  A table lives as long as the process does (a few KiB a stream).
-constexpr int kCfRing = 4;
-struct CfStage {
-    CfPlan *h[kCfRing] = {};
-    size_t cap[kCfRing] = {};  // plans
-    hipEvent_t read[kCfRing] = {};
-    int next = 0;
-};
-std::unordered_map<hipStream_t, CfStage> g_cf_stage;
-hipError_t cf_upload(hipStream_t s, void *table_dev, const std::vector<CfPlan> &plans) {
-    CfStage &st = g_cf_stage[s];
-    const int k = st.next;
-    hipError_t e;
-    if (st.read[k]) {
-        if ((e = hipEventSynchronize(st.read[k])) != hipSuccess) return e;
-    } else if ((e = hipEventCreateWithFlags(&st.read[k], hipEventDisableTiming)) != hipSuccess) {
-        st.read[k] = nullptr;
-        return e;
-    }
-    if (st.cap[k] < plans.size()) {
-        if (st.h[k]) (void)hipHostFree(st.h[k]);
-        st.h[k] = nullptr, st.cap[k] = 0;
-        size_t cap = 64;
-        while (cap < plans.size()) cap *= 2;
-        if ((e = hipHostMalloc(reinterpret_cast<void **>(&st.h[k]), cap * sizeof(CfPlan), hipHostMallocDefault)) != hipSuccess) {
-            st.h[k] = nullptr;
-            return e;
-        }
-        st.cap[k] = cap;
-    }
-    std::copy(plans.begin(), plans.end(), st.h[k]);
-    if ((e = hipMemcpyAsync(table_dev, st.h[k], plans.size() * sizeof(CfPlan), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipEventRecord(st.read[k], s)) != hipSuccess) return e;
-    st.next = (k + 1) % kCfRing;
-    return hipSuccess;
-}
-
 inline int vec3(const void *a, const void *b, const void *dst) {
     auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     return (al(a) ? 1 : 0) | (al(b) ? 2 : 0) | (al(dst) ? 4 : 0);
@@ -382,7 +343,10 @@ rh_status rh_crossfade(const uint64_t *pairs_words_host, uint32_t n_pairs, uint6
     void *scratch = nullptr;
     RH_HIP_TRY(rh::stream_scratch(s, table_bytes + rows_bytes, &scratch, hold));
     if (!fused.empty()) {
-        RH_HIP_TRY(cf_upload(s, scratch, fused));
+        char *host = nullptr;  // the plan table's way to the device: the stream's table ring (rh_common.h)
+        RH_HIP_TRY(rh::table_stage(s, fused.size() * sizeof(CfPlan), &host));
+        memcpy(host, fused.data(), fused.size() * sizeof(CfPlan));
+        RH_HIP_TRY(rh::table_send(s, scratch));
         const uint64_t tiles = (most + kCfTile - 1) / kCfTile;
         if (tiles > 0x7fffffffull) return RH_ERR_UNSUPPORTED;
         for (size_t first = 0; first < fused.size(); first += 65535) {

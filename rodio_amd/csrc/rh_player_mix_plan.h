@@ -4,57 +4,28 @@
 // Building the kernel tables and launching are rh_player_mix_block's.  Nothing here allocates.
 #pragma once
 #include <cstdint>
-#include <numeric>
 
 #include "../../include/rodio_hip.h"
+#include "rh_mix_plan.h"
 
 namespace rh {
 namespace playermix {
 
-constexpr uint32_t kChunk = 32;     // sources a launch (the table travels by value in the kernel-argument segment)
-constexpr uint32_t kGroup = 4;      // ... walked in groups of this many by the general kernel: a launch's slots are whole groups
-constexpr uint32_t kRates = 4;      // ... of at most this many different (F, T, r0): k_wide_mix's kWideRates
+using mixplan::check_src;  // the fields the entry shares with rh_wide_mix_block, and the reach of the block's taps: a block is not cut into launches
+using mixplan::kChunk;     // sources a launch
+using mixplan::kGroup;     // ... walked in groups of this many by the general kernel: a launch's slots are whole groups
+using mixplan::kRates;     // ... of at most this many different (F, T, r0)
+using mixplan::Rate;
+using mixplan::Reach;
 // The step rule's index -- sample k = f * src_channels + c, counted from `data` -- stays below this for every tap of a block (rh_live.hip's
 // bound: with the phase of the first sample inside its period it then fits 32 bits).
 constexpr uint64_t kMaxStepSamples = 1ull << 30;
 
 enum Kernel { kGeneral = 0, kStereo = 1 };  // k_player_mix / k_player_mix_stereo
 
-struct Rate {
-    uint32_t F, T;  // reduced rates (an unused slot: F = 0, T = 1)
-    uint32_t r0;    // the block's phase
-    float Tf;
-};
-
-// What the taps of a block reach of one source.
-struct Reach {
-    uint32_t F, T;     // from_rate / to_rate reduced
-    uint64_t frames;   // source frames, counted from data: 0 .. frames - 1
-    uint64_t samples;  // samples of the source's stream, counted from data, up to the last one a tap reads: what a factor table must cover
-};
-
 // Entries of a table that covers samples [0, n) of a stream whose first sample lies `at` behind a multiple of the period (rh_amplify_steps' rule).
 inline uint64_t steps_needed(uint64_t at, uint64_t period, uint64_t n) { return n ? (at + n - 1) / period + 1 : 0; }
 inline uint64_t entries_needed(uint64_t first, uint64_t period, uint64_t n) { return steps_needed(first % period, period, n); }
-
-// rh_wide_mix_block's answers about the fields the two entries share (a source with frames > 0), and the reach of the block's taps.
-// A block is not cut into launches: one whose positions phase + j F leave 32 bits is refused.
-inline rh_status check_src(const rh_wide_src &x, uint32_t channels, uint32_t to_rate, uint64_t out_frames, Reach *r) {
-    if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-    const uint32_t g = std::gcd(x.from_rate, to_rate);
-    r->F = x.from_rate / g, r->T = to_rate / g;
-    if ((uint64_t)r->F * r->T > 0xffffffffull) return RH_ERR_UNSUPPORTED;  // the reference multiplies in u32 (sample_rate.rs:157,173)
-    if (x.phase >= r->T) return RH_ERR_INVALID;
-    if (out_frames > (0xffffffffull - r->T) / r->F) return RH_ERR_UNSUPPORTED;
-    // the first tap of the last frame the source reaches, and the second one where that frame has it
-    const uint64_t il = ((uint64_t)x.phase + (x.frames - 1) * r->F) / r->T;
-    const uint64_t lastf = il + (r->F != r->T && il < x.last ? 1 : 0);
-    r->frames = lastf + 1;
-    // channels.rs:59-70: output channel c reads input channel c (c < from), channel 1 of a mono source its only one: the highest input channel read
-    // is min(from, to) - 1
-    r->samples = lastf * x.channels + (x.channels < channels ? x.channels : channels);
-    return RH_OK;
-}
 
 // A ramp of `kind` (0 none, 1 LinearGainRamp, 2 ... with clamp_end) at the block's first frame, given what rhrows::make_ramp made of it
 // (step_ns = 1e9 / rate, done_frame = ceil(duration / step_ns)): 0 no multiply, 1 ONE constant factor for the whole block -- the ramp has run
@@ -92,14 +63,8 @@ inline rh_status check(const float *dst, uint32_t channels, uint32_t to_rate, ui
     return RH_OK;
 }
 
-// One launch: up to kChunk sources in insertion order, each with its slot of r.
-struct Launch {
-    Rate r[kRates];
-    uint32_t nr;            // slots of r in use
-    uint32_t n;             // sources (0: no source reaches the block, the launch writes zeros)
-    uint32_t src[kChunk];   // their indices in the caller's table
-    uint32_t rate[kChunk];  // their slots
-    bool cont;              // it continues from the partial sum an earlier launch of the call stored
+// One launch: up to kChunk sources in insertion order, each with its slot of r (mixplan::RateLaunch), and its kernel.
+struct Launch : mixplan::RateLaunch {
     Kernel kernel;
 };
 
@@ -116,40 +81,22 @@ inline Kernel kernel_of(const Launch &L, uint32_t channels, uint64_t out_frames,
     return kStereo;
 }
 
-// The launches of a call that check() has passed, in order: emit(const Launch &) for each.  A launch is full at kChunk sources, and goes early
-// when a source brings a fifth (F, T, r0): what has been gathered goes first, and the sum continues from the stored partial sum.
+// The launches of a call that check() has passed, in order: emit(const Launch &) for each (mixplan::walk_rates: full at kChunk sources, early
+// at a fifth (F, T, r0)).
 template <class Emit>
 inline void walk(uint32_t channels, uint32_t to_rate, uint64_t out_frames, const rh_wide_src *srcs, uint32_t n_sources, bool dst_on_8, Emit &&emit) {
-    Launch L;
-    bool cont = false;
-    auto clear = [&]() {
-        for (uint32_t q = 0; q < kRates; ++q) L.r[q] = Rate{0u, 1u, 0u, 1.0f};
-        L.nr = 0, L.n = 0;
-    };
-    auto flush = [&]() {
-        L.cont = cont;
-        L.kernel = kernel_of(L, channels, out_frames, srcs, dst_on_8);
-        emit(static_cast<const Launch &>(L));
-        cont = true;
-        clear();
-    };
-    clear();
-    for (uint32_t s = 0; s < n_sources; ++s) {
-        const rh_wide_src &x = srcs[s];
-        if (x.frames == 0) continue;
-        const uint32_t g = std::gcd(x.from_rate, to_rate);
-        const uint32_t F = x.from_rate / g, T = to_rate / g;
-        uint32_t q = 0;
-        while (q < L.nr && !(L.r[q].F == F && L.r[q].T == T && L.r[q].r0 == x.phase)) ++q;
-        if (q == L.nr && L.nr == kRates) {
-            flush();
-            q = 0;
-        }
-        if (q == L.nr) L.r[L.nr++] = Rate{F, T, x.phase, (float)T};
-        L.src[L.n] = s, L.rate[L.n] = q;
-        if (++L.n == kChunk) flush();
-    }
-    if (L.n || !cont) flush();
+    mixplan::walk_rates<Launch>(
+        n_sources, true,
+        [&](uint32_t s, uint32_t *F, uint32_t *T, uint32_t *r0, uint64_t *) {
+            if (srcs[s].frames == 0) return false;
+            mixplan::reduce(srcs[s].from_rate, to_rate, F, T);
+            *r0 = srcs[s].phase;
+            return true;
+        },
+        [&](Launch &L) {
+            L.kernel = kernel_of(L, channels, out_frames, srcs, dst_on_8);
+            emit(static_cast<const Launch &>(L));
+        });
 }
 
 }  // namespace playermix

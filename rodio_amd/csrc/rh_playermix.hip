@@ -16,41 +16,21 @@
 // The host decisions are rh_player_mix_plan.h's; the source table travels by value as a kernel argument (32 sources a launch; more
 // continue from the stored partial sum).
 #include "rh_common.h"
+#include "rh_mix_dev.h"
 #include "rh_player_mix_plan.h"
 #include "rh_rows_dev.h"
 
 namespace {
 
+namespace md = rh::mixdev;
 namespace pm = rh::playermix;
 
 constexpr int kBlock = 256;
 constexpr int kGroup = (int)pm::kGroup;
 
-// rh_live.hip's step index (the copy of rh_spatialmix.hip): x / d for x < 2^32, 1 <= d <= 2^31 by the round-up method, no division per sample.
-struct StepDiv {
-    uint32_t phase;  // (first % period), reduced as below
-    uint32_t m, s1, s2;
-    __device__ __forceinline__ uint32_t step(uint32_t i) const {
-        const uint32_t x = phase + i;
-        const uint32_t t = __umulhi(x, m);
-        return (t + ((x - t) >> s1)) >> s2;
-    }
-};
-// The table index of sample i (< n <= 2^30) of a block whose first sample lies `at` samples behind a multiple of `period` (>= 1).
-StepDiv step_div(uint64_t at, uint64_t period, uint64_t n) {
-    uint64_t d = period, phase = at % period;
-    if (d > (1ull << 31)) {
-        // at most one boundary inside the block, at i = period - phase: the same quotient with d = 2^31 and the phase moved so that the
-        // boundary stays where it is (i < 2^30 keeps phase + i below 2^32)
-        const uint64_t t = d - phase;
-        d = 1ull << 31;
-        phase = t >= n ? 0 : d - t;
-    }
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-    return StepDiv{(uint32_t)phase, (uint32_t)m, l < 1 ? l : 1u, l > 1 ? l - 1 : 0u};
-}
+using rh::mixplan::StepDiv;  // rh_live.hip's step index: sample k of the source's stream, counted from data -> entry of a step table
+using rh::mixplan::step_div;
+using rh::mixplan::kStepNone;
 
 struct PmDesc {
     const float *data;     // the frame that holds the first tap of the block's first output frame
@@ -82,18 +62,7 @@ template <bool CONT>
 __global__ __launch_bounds__(kBlock) void k_player_mix(float *__restrict__ dst, uint32_t to_ch, uint32_t out_frames, const PmTable tbl, uint32_t n_sources) {
     const uint64_t total = (uint64_t)out_frames * to_ch;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    {
-        // (k_wide_mix: the table is read through the scalar cache, and the first wave of a CU would miss on its lines one after the
-        //  other.  One word of every line is asked for here, all requests in flight at once.)
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(&tbl);
-        constexpr uint32_t kLines = (sizeof(PmTable) + 63) / 64;
-        uint32_t t[kLines], touch = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) t[q] = w[q * 16u];
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) touch |= t[q];
-        asm volatile("" ::"s"(touch));
-    }
+    md::touch_table(tbl);  // (the first wave of a CU would miss on the table's lines one after the other)
     for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < total; o += stride) {
         const uint32_t j = (uint32_t)(o / to_ch);
         const uint32_t c = (uint32_t)(o - (uint64_t)j * to_ch);
@@ -115,8 +84,8 @@ __global__ __launch_bounds__(kBlock) void k_player_mix(float *__restrict__ dst, 
                 const uint32_t q = d.rate;
                 const uint32_t i = q == 0 ? il[0] : (q == 1 ? il[1] : (q == 2 ? il[2] : il[3]));
                 wv[u] = q == 0 ? w[0] : (q == 1 ? w[1] : (q == 2 ? w[2] : w[3]));
-                const uint32_t k = c < d.ch ? c : 0u;                          // channels.rs:59-70: k < from: the input channel; k == 1 of a mono source: its only one;
-                on[u] = j < d.frames && (c < d.ch || (c == 1u && d.ch == 1u));  // otherwise 0.0
+                const uint32_t k = md::in_channel(c, d.ch);
+                on[u] = j < d.frames && md::has_channel(c, d.ch);
                 lerp[u] = on[u] && d.Tf != 0.0f && i < d.last;
                 const uint32_t ia = on[u] ? i : 0u, ib = lerp[u] ? ia + 1u : ia;
                 a[u] = d.data[(uint64_t)ia * d.ch + k];
@@ -187,16 +156,8 @@ __global__ __launch_bounds__(kBlock) void k_player_mix_stereo(float2 *__restrict
     const uint32_t s0 = wave * kFastGroup;
     const bool mine = s0 < n_sources;  // (wave-uniform: a wave without sources only keeps the barriers)
     if (mine) {
-        // (k_player_mix: a word of every line of the wave's descriptors, all requests in flight at once)
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(&tbl.d[s0]);
-        constexpr uint32_t kLines = (kFastGroup * sizeof(PmFastSrc)) / 64;
-        uint32_t t[kLines + 1], touch = 0;
-        t[kLines] = tbl.F;
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) t[q] = w[q * 16u];
-#pragma unroll
-        for (uint32_t q = 0; q <= kLines; ++q) touch |= t[q];
-        asm volatile("" ::"s"(touch));
+        // (a word of every line of the wave's descriptors, and the header, all requests in flight at once)
+        md::touch_lines<(kFastGroup * sizeof(PmFastSrc)) / 64>(reinterpret_cast<const uint32_t *>(&tbl.d[s0]), tbl.F);
     }
     for (uint32_t base = blockIdx.x * kFastFrames; base < out_frames; base += gridDim.x * kFastFrames) {  // (host: out_frames < 2^31; the same trips for every lane)
         const bool act = base + lane < out_frames;
@@ -295,7 +256,7 @@ rh_status rh_player_mix_block(float *dst, uint32_t channels, uint32_t to_rate, u
     };
     auto adapters_of = [&](uint32_t s) {
         const rh_wide_src &x = srcs_host[s];
-        Adapters a{pm::kRampNone, 1.0f, 0, rhrows::Ramp{0, 0, 0.0f, 0.0f, 0.0f, 1.0f}, nullptr, StepDiv{0u, 1u, 0u, 0u}};
+        Adapters a{pm::kRampNone, 1.0f, 0, rhrows::Ramp{0, 0, 0.0f, 0.0f, 0.0f, 1.0f}, nullptr, kStepNone};
         if (ramps_host && ramps_host[4 * (size_t)s] != 0) {
             const uint64_t *w = ramps_host + 4 * (size_t)s;
             a.r = rhrows::make_ramp((uint32_t)w[3], w[1], ramp_gains_host[2 * (size_t)s], ramp_gains_host[2 * (size_t)s + 1], w[0] == 2);
@@ -342,7 +303,7 @@ rh_status rh_player_mix_block(float *dst, uint32_t channels, uint32_t to_rate, u
         }
         // whole groups: slots that reach no frame (and point at something readable: the first source's first tap, or dst where there is no source)
         const float *readable = L.n ? tbl.d[0].data : dst;
-        while (k % pm::kGroup) tbl.d[k++] = PmDesc{readable, nullptr, 1u, 0u, 0u, 0u, 0.0f, 0.0f, pm::kRampNone, 1.0f, StepDiv{0u, 1u, 0u, 0u}, 0, rhrows::Ramp{0, 0, 0.0f, 0.0f, 0.0f, 1.0f}};
+        while (k % pm::kGroup) tbl.d[k++] = PmDesc{readable, nullptr, 1u, 0u, 0u, 0u, 0.0f, 0.0f, pm::kRampNone, 1.0f, kStepNone, 0, rhrows::Ramp{0, 0, 0.0f, 0.0f, 0.0f, 1.0f}};
         const uint64_t total = (uint64_t)nf * channels;
         const dim3 grid(rh::grid_for((size_t)total, kBlock, 256u * 16u));
         if (L.cont) hipLaunchKernelGGL(k_player_mix<true>, grid, dim3(kBlock), 0, st, dst, channels, nf, tbl, k);

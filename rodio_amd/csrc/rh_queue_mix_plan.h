@@ -12,21 +12,19 @@
 // is SILENT behind it; without, the chain ends with the sounds and the queue has ENDED.  Either way it adds nothing behind.
 #pragma once
 #include <cstdint>
-#include <numeric>
 #include <vector>
 
 #include "../../include/rodio_hip.h"
-#include "rh_loop_mix_plan.h"
-#include "rh_player_mix_plan.h"
+#include "rh_mix_plan.h"
 
 namespace rh {
 namespace queuemix {
 
-using loopmix::Div;
-using loopmix::div_u32;
-using loopmix::kChainSamples;
-using loopmix::make_div;
-using loopmix::span_out;
+using mixplan::Div;
+using mixplan::div_u32;
+using mixplan::kChainSamples;
+using mixplan::make_div;
+using mixplan::span_out;
 
 enum : uint64_t { kPlaying = 0, kSilent = 1, kEnded = 2 };
 
@@ -110,8 +108,7 @@ struct Conv {
     uint64_t M;       // output frames
 };
 inline rh_status convert(const Chain &c, uint32_t to_rate, Conv *v) {
-    const uint32_t g = std::gcd(c.rate, to_rate);
-    v->F = c.rate / g, v->T = to_rate / g;
+    mixplan::reduce(c.rate, to_rate, &v->F, &v->T);
     if ((uint64_t)v->F * v->T > 0xffffffffull) return RH_ERR_UNSUPPORTED;  // the reference multiplies in u32 (sample_rate.rs:157,173)
     if (c.n % c.ch) return RH_ERR_UNSUPPORTED;                             // a chain that cuts a frame
     v->frames = c.n / c.ch;
@@ -224,7 +221,7 @@ struct Taps {
     uint32_t num;  // (position) mod T: the lerp's weight over T
 };
 // Output frame m (m0 <= m < m0 + count) of a segment.  Every intermediate fits 32 bits for a call check() has passed.
-RH_LOOP_HD Taps locate(const Seg &g, uint32_t m) {
+RH_MIX_HD Taps locate(const Seg &g, uint32_t m) {
     const uint32_t j = g.prior + (m - g.m0);
     const uint32_t pos = g.r0 + j * g.F;
     Taps t;
@@ -234,7 +231,7 @@ RH_LOOP_HD Taps locate(const Seg &g, uint32_t m) {
     return t;
 }
 // The segment of `n` that holds output frame m, or n where none does (segments are in order and do not overlap).
-RH_LOOP_HD uint32_t find_seg(const Seg *g, uint32_t n, uint32_t m) {
+RH_MIX_HD uint32_t find_seg(const Seg *g, uint32_t n, uint32_t m) {
     uint32_t lo = 0, hi = n;  // the first segment that ends behind m
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -244,7 +241,7 @@ RH_LOOP_HD uint32_t find_seg(const Seg *g, uint32_t n, uint32_t m) {
     return lo < n && g[lo].m0 <= m ? lo : n;
 }
 // The piece of `n` (n >= 1, the first one's start is 0) that holds sample e of the chain: the last one with start <= e.
-RH_LOOP_HD uint32_t find_piece(const Piece *p, uint32_t n, uint64_t e) {
+RH_MIX_HD uint32_t find_piece(const Piece *p, uint32_t n, uint64_t e) {
     uint32_t lo = 0, hi = n;
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -274,10 +271,10 @@ inline rh_status plan(const float *dst, uint32_t channels, uint32_t to_rate, uin
         const Sounds q = Sounds{sounds, gains}.from(at);
         at += n_sounds;
         Src d{(uint32_t)p->segs.size(), 0u};
-        if (n_sounds == 0) {  // rh_wide_mix_block's source (rh_player_mix_plan.h holds its answers)
+        if (n_sounds == 0) {  // rh_wide_mix_block's source
             if (x.frames) {
-                playermix::Reach r;
-                const rh_status st = playermix::check_src(x, channels, to_rate, out_frames, &r);
+                mixplan::Reach r;
+                const rh_status st = mixplan::check_src(x, channels, to_rate, out_frames, &r);
                 if (st != RH_OK) return st;
                 p->segs.push_back(Seg{0u, (uint32_t)x.frames, 0u, x.channels, r.F, r.T, r.F == r.T ? 0.0f : (float)r.T, x.phase, x.last, (uint32_t)p->pieces.size(), 1u, make_div(r.T), {0u, 0u, 0u}});
                 p->pieces.push_back(Piece{x.data, 0u, x.gain});

@@ -14,15 +14,15 @@
 // The tables live in device memory: one copy in front of the launch on the same stream, as rh_wide_mix_batch takes its tables there, so
 // neither sources nor sounds nor seams multiply launches.
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
 #include "rh_common.h"
+#include "rh_mix_dev.h"
 #include "rh_queue_mix_plan.h"
 
 namespace {
 
 namespace qm = rh::queuemix;
+namespace md = rh::mixdev;
 
 constexpr int kBlock = 256;
 
@@ -69,10 +69,9 @@ __global__ __launch_bounds__(kBlock) void k_queue_mix(float *__restrict__ dst, u
                 }
                 for (; q < d.seg_count; ++q) {
                     const qm::Seg g = gs[q];
-                    // channels.rs:59-70: k < from: the input channel; k == 1 of a mono source: its only one; otherwise 0.0
-                    if (m - g.m0 < g.count && (c < g.ch || (c == 1u && g.ch == 1u))) {
+                    if (m - g.m0 < g.count && md::has_channel(c, g.ch)) {
                         const qm::Taps t = qm::locate(g, m);
-                        const uint64_t ea = (uint64_t)t.i * g.ch + (c < g.ch ? c : 0u), eb = t.lerp ? ea + g.ch : ea;
+                        const uint64_t ea = (uint64_t)t.i * g.ch + md::in_channel(c, g.ch), eb = t.lerp ? ea + g.ch : ea;
                         const qm::Piece *__restrict__ p = pieces + g.piece_first;
                         float x = 0.0f, y = 0.0f;  // (the +0.0 of a keep-alive tail meets no gain)
                         if (g.piece_count == 1u) {  // (a plain source, or a chain inside one sound: the indices may leave 32 bits)
@@ -104,54 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_queue_mix(float *__restrict__ dst, u
     }
 }
 
-// The tables' way to the device, as rh_wide_mix_batch's go (rh_widebatch.hip): page-locked tables, a ring of them per stream, each rewritten
-// only after an event recorded behind the copy that read it has fired.  Used under the stream's scratch lock.  A table lives as long as the
-// process does.
-constexpr int kRing = 4;
-struct Stage {
-    char *h[kRing] = {};
-    size_t cap[kRing] = {};  // bytes
-    hipEvent_t read[kRing] = {};
-    int next = 0;
-};
-std::unordered_map<hipStream_t, Stage> g_stage;
-std::mutex g_stage_mu;  // (the map; a Stage is its stream's)
 inline size_t pad64(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
-
-hipError_t upload(hipStream_t s, void *table_dev, const qm::Plan &p, size_t segs_at, size_t pieces_at, size_t bytes) {
-    Stage *stp;
-    {
-        std::lock_guard<std::mutex> lk(g_stage_mu);
-        stp = &g_stage[s];
-    }
-    Stage &st = *stp;
-    const int k = st.next;
-    hipError_t e;
-    if (st.read[k]) {
-        if ((e = hipEventSynchronize(st.read[k])) != hipSuccess) return e;
-    } else if ((e = hipEventCreateWithFlags(&st.read[k], hipEventDisableTiming)) != hipSuccess) {
-        st.read[k] = nullptr;
-        return e;
-    }
-    if (st.cap[k] < bytes) {
-        if (st.h[k]) (void)hipHostFree(st.h[k]);
-        st.h[k] = nullptr, st.cap[k] = 0;
-        size_t cap = 1 << 16;
-        while (cap < bytes) cap *= 2;
-        if ((e = hipHostMalloc(reinterpret_cast<void **>(&st.h[k]), cap, hipHostMallocDefault)) != hipSuccess) {
-            st.h[k] = nullptr;
-            return e;
-        }
-        st.cap[k] = cap;
-    }
-    memcpy(st.h[k], p.srcs.data(), p.srcs.size() * sizeof(qm::Src));
-    memcpy(st.h[k] + segs_at, p.segs.data(), p.segs.size() * sizeof(qm::Seg));
-    memcpy(st.h[k] + pieces_at, p.pieces.data(), p.pieces.size() * sizeof(qm::Piece));
-    if ((e = hipMemcpyAsync(table_dev, st.h[k], bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipEventRecord(st.read[k], s)) != hipSuccess) return e;
-    st.next = (k + 1) % kRing;
-    return hipSuccess;
-}
 
 }  // namespace
 
@@ -183,7 +135,12 @@ rh_status rh_queue_mix_block(float *dst, uint32_t channels, uint32_t to_rate, ui
     std::unique_lock<std::mutex> hold;
     void *scratch = nullptr;
     RH_HIP_TRY(rh::stream_scratch(s, bytes, &scratch, hold));
-    RH_HIP_TRY(upload(s, scratch, plan, segs_at, pieces_at, bytes));
+    char *host = nullptr;  // the tables' way to the device: the stream's table ring (rh_common.h)
+    RH_HIP_TRY(rh::table_stage(s, bytes, &host));
+    memcpy(host, plan.srcs.data(), plan.srcs.size() * sizeof(qm::Src));
+    memcpy(host + segs_at, plan.segs.data(), plan.segs.size() * sizeof(qm::Seg));
+    memcpy(host + pieces_at, plan.pieces.data(), plan.pieces.size() * sizeof(qm::Piece));
+    RH_HIP_TRY(rh::table_send(s, scratch));
     const char *base = static_cast<const char *>(scratch);
     hipLaunchKernelGGL(k_queue_mix, grid, dim3(kBlock), 0, s, dst, channels, nf, reinterpret_cast<const qm::Src *>(base), reinterpret_cast<const qm::Seg *>(base + segs_at),
                        reinterpret_cast<const qm::Piece *>(base + pieces_at), n_sources);

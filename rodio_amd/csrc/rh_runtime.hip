@@ -103,8 +103,17 @@ struct Scratch {
     size_t cap = 0;
     ScratchAux aux{0, 0, 0};
 };
+constexpr int kTableRing = 4;
+struct TableRing {
+    char *h[kTableRing] = {};
+    size_t cap[kTableRing] = {};  // bytes
+    hipEvent_t read[kTableRing] = {};
+    int next = 0;
+    size_t staged = 0;  // bytes of h[next] that table_stage handed out and table_send has not sent yet
+};
 std::mutex g_scratch_mu;
 std::unordered_map<hipStream_t, Scratch> g_scratch;
+std::unordered_map<hipStream_t, TableRing> g_table_ring;  // (under g_scratch_mu, as a stream's scratch: its users hold stream_scratch's lock)
 }  // namespace
 hipError_t stream_scratch(hipStream_t s, size_t bytes, void **out, std::unique_lock<std::mutex> &hold, ScratchAux **aux) {
     hold = std::unique_lock<std::mutex>(g_scratch_mu);
@@ -138,12 +147,59 @@ static void distrust_stream_scratch() {
     std::lock_guard<std::mutex> lk(g_scratch_mu);
     for (auto &kv : g_scratch) kv.second.aux = ScratchAux{0, 0, 0};
 }
+hipError_t table_stage(hipStream_t s, size_t bytes, char **host) {
+    TableRing &r = g_table_ring[s];
+    const int k = r.next;
+    hipError_t e;
+    if (r.read[k]) {
+        if ((e = hipEventSynchronize(r.read[k])) != hipSuccess) return e;
+    } else if ((e = hipEventCreateWithFlags(&r.read[k], hipEventDisableTiming)) != hipSuccess) {
+        r.read[k] = nullptr;
+        return e;
+    }
+    if (r.cap[k] < bytes) {
+        if (r.h[k]) (void)hipHostFree(r.h[k]);
+        r.h[k] = nullptr, r.cap[k] = 0;
+        size_t cap = 1 << 16;
+        while (cap < bytes) cap *= 2;
+        if ((e = hipHostMalloc(reinterpret_cast<void **>(&r.h[k]), cap, hipHostMallocDefault)) != hipSuccess) {
+            r.h[k] = nullptr;
+            return e;
+        }
+        r.cap[k] = cap;
+    }
+    *host = r.h[k];
+    r.staged = bytes;
+    return hipSuccess;
+}
+hipError_t table_send(hipStream_t s, void *dev) {
+    TableRing &r = g_table_ring[s];
+    const int k = r.next;
+    const size_t bytes = r.staged;
+    r.staged = 0;
+    if (!bytes || !r.h[k]) return hipErrorInvalidValue;  // (nothing staged: not behind a table_stage of this stream)
+    hipError_t e;
+    if ((e = hipMemcpyAsync(dev, r.h[k], bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+    if ((e = hipEventRecord(r.read[k], s)) != hipSuccess) return e;
+    r.next = (k + 1) % kTableRing;
+    return hipSuccess;
+}
+// The stream's scratch and its table ring go (the caller has synchronised the stream: nothing reads either any more).
 static void drop_stream_scratch(hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_scratch_mu);
     auto it = g_scratch.find(s);
-    if (it == g_scratch.end()) return;
-    if (it->second.p) (void)hipFree(it->second.p);
-    g_scratch.erase(it);
+    if (it != g_scratch.end()) {
+        if (it->second.p) (void)hipFree(it->second.p);
+        g_scratch.erase(it);
+    }
+    auto rt = g_table_ring.find(s);
+    if (rt != g_table_ring.end()) {
+        for (int k = 0; k < kTableRing; ++k) {
+            if (rt->second.read[k]) (void)hipEventDestroy(rt->second.read[k]);
+            if (rt->second.h[k]) (void)hipHostFree(rt->second.h[k]);
+        }
+        g_table_ring.erase(rt);
+    }
 }
 hipError_t counters_add(uint32_t *ctl, uint32_t d_ticket, uint32_t n_shards, uint32_t d_shards, hipStream_t s) {
     hipLaunchKernelGGL(k_counters_add, dim3(1), dim3(64), 0, s, ctl, d_ticket, n_shards < 63u ? n_shards : 63u, d_shards);

@@ -15,52 +15,24 @@
 // in different steps).  A lane walks the sources in insertion order and adds: the reference's rounding sequence, bit for bit.
 // 4 in_ch N bytes in per source (the second tap of a frame is the first tap of the next: L1 / L2), 4 C M out.
 // The source table travels by value as a kernel argument (32 sources a launch; more continue from the stored partial sum).
-#include <numeric>
-
 #include "rh_common.h"
+#include "rh_mix_plan.h"
 
 namespace {
 
+namespace mp = rh::mixplan;
+using mp::StepDiv;  // rh_live.hip's step index: sample k of the emitter's output, counted from a launch's first one -> entry of a step table
+using mp::step_div;
+
 constexpr int kBlock = 256;
-constexpr uint32_t kSpChunk = 32;  // sources a launch (the table: 2.6 KiB of the 4 KiB kernel-argument segment)
-constexpr int kSpGroup = 4;        // ... walked in groups of this many, whose loads leave together
-constexpr uint32_t kSpRates = 4;   // ... of at most this many different (rate, phase) pairs, as k_wide_mix
+constexpr uint32_t kSpChunk = mp::kChunk;  // sources a launch (the table: 2.6 KiB of the 4 KiB kernel-argument segment)
+constexpr int kSpGroup = (int)mp::kGroup;  // ... walked in groups of this many, whose loads leave together
+constexpr uint32_t kSpRates = mp::kRates;  // ... of at most this many different (rate, phase) pairs, as k_wide_mix
 // A launch reaches at most this many samples of an emitter's output: every in-launch index, plus the phase of the first one inside
 // its period, then fits in 32 bits (rh_live.hip's bound).
 constexpr uint64_t kMaxLaunchSamples = 1ull << 30;
+using SpRate = mp::Rate;  // r0: (phase + j0 F) mod T
 
-// rh_live.hip's step index: x / d for x < 2^32, 1 <= d <= 2^31 by the round-up method (Granlund-Montgomery), no division per sample.
-struct StepDiv {
-    uint32_t phase;  // (first % period), reduced as below
-    uint32_t m, s1, s2;
-    __device__ __forceinline__ uint32_t step(uint32_t i) const {
-        const uint32_t x = phase + i;
-        const uint32_t t = __umulhi(x, m);
-        return (t + ((x - t) >> s1)) >> s2;
-    }
-};
-// The table index of sample i (< n <= 2^30) of a launch whose first sample lies `at` samples behind a step boundary's multiple
-// (at = first % period + samples in front of the launch), for `period` >= 1.
-StepDiv step_div(uint64_t at, uint64_t period, uint64_t n) {
-    uint64_t d = period, phase = at % period;
-    if (d > (1ull << 31)) {
-        // at most one boundary inside the launch, at i = period - phase: the same quotient with d = 2^31 and the phase moved so that
-        // the boundary stays where it is (i < 2^30 keeps phase + i below 2^32)
-        const uint64_t t = d - phase;
-        d = 1ull << 31;
-        phase = t >= n ? 0 : d - t;
-    }
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    const uint64_t m = ((1ull << 32) * ((1ull << l) - d)) / d + 1;
-    return StepDiv{(uint32_t)phase, (uint32_t)m, l < 1 ? l : 1u, l > 1 ? l - 1 : 0u};
-}
-
-struct SpRate {
-    uint32_t F, T;  // reduced rates (an unused slot: F = 0, T = 1)
-    uint32_t r0;    // (phase + j0 F) mod T
-    float Tf;
-};
 struct SpDesc {
     const float *data;     // the frame that holds the first tap of the launch's first output frame
     const float *gains;    // the entry of that frame's first sample, [steps][channels]
@@ -306,10 +278,8 @@ rh_status rh_spatial_mix_block(float *dst, uint32_t channels, uint32_t to_rate, 
     // Everything is checked before the first launch: a call that fails has written nothing.
     auto factors_of = [&](uint32_t s) { return factors_dev_host ? factors_dev_host[s] : nullptr; };
     // (worked out where it is needed, not kept: the call allocates nothing)
-    auto reduce = [&](uint32_t s) {
-        const rh_wide_src &x = srcs_host[s];
-        const uint32_t g = std::gcd(x.from_rate, to_rate);
-        Red r{x.from_rate / g, to_rate / g, gain_steps_host[3 * (size_t)s] % gain_steps_host[3 * (size_t)s + 1], 0};
+    auto red_of = [&](uint32_t s, const mp::Rate &rt) {  // (rt: the source's slot, which holds its reduced rates)
+        Red r{rt.F, rt.T, gain_steps_host[3 * (size_t)s] % gain_steps_host[3 * (size_t)s + 1], 0};
         if (factors_of(s)) r.f0 = factor_steps_host[3 * (size_t)s] % factor_steps_host[3 * (size_t)s + 1];
         return r;
     };
@@ -317,13 +287,11 @@ rh_status rh_spatial_mix_block(float *dst, uint32_t channels, uint32_t to_rate, 
     for (uint32_t s = 0; s < n_sources; ++s) {
         const rh_wide_src &x = srcs_host[s];
         if (x.frames == 0) continue;
-        // wide_check_src's rule (rh_widemix.hip) for the fields the two entries share
-        if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-        const uint32_t g = std::gcd(x.from_rate, to_rate);
-        const uint32_t F = x.from_rate / g, T = to_rate / g;
-        if ((uint64_t)F * T > 0xffffffffull) return RH_ERR_UNSUPPORTED;  // the reference multiplies in u32 (sample_rate.rs:157,173)
-        if (x.phase >= T) return RH_ERR_INVALID;
-        uint64_t fit = (0xffffffffull - T) / F;
+        // the fields the entry shares with rh_wide_mix_block
+        uint32_t F, T;
+        uint64_t fit;
+        const rh_status shared = mp::check_src(x, to_rate, out_frames, &F, &T, &fit);
+        if (shared != RH_OK) return shared;
         // ... and the step rule's: the last source frame a launch touches, i <= (T - 1 + (nf - 1) F) / T + 1, times `channels` stays below 2^30
         const uint64_t fit_steps = (kMaxLaunchSamples / channels - 2) * T / F + 1;
         if (fit_steps < fit) fit = fit_steps;
@@ -349,117 +317,81 @@ rh_status rh_spatial_mix_block(float *dst, uint32_t channels, uint32_t to_rate, 
     // Alike sources (mono, one rate and phase, into a stereo mix on an 8-byte boundary): the frames in front of the first one that ends -- or
     // whose last frame a tap reaches -- go to the fast kernel as a launch of their own, the rest to the general one (rh_wide_mix_block's cut).
     const bool fast_ok = channels == 2 && (reinterpret_cast<uintptr_t>(dst) & 7u) == 0;
-    uint64_t j_uni = 0;
-    if (fast_ok) {
-        bool alike = true;
-        int first = -1;
-        uint64_t upto = out_frames;
-        for (uint32_t s = 0; s < n_sources && alike; ++s) {
-            const rh_wide_src &x = srcs_host[s];
-            if (x.frames == 0) continue;
-            if (first < 0) first = (int)s;
-            const Red r = reduce(s);
-            alike = x.channels == 1 && x.from_rate == srcs_host[first].from_rate && x.phase == srcs_host[first].phase;
-            uint64_t u = x.frames;
-            if (x.last != 0xffffffffu && r.F != r.T) {  // il(j) >= last  <=>  phase + j F >= last T
-                const uint64_t need = (uint64_t)x.last * r.T;
-                const uint64_t jl = need > x.phase ? (need - x.phase + r.F - 1) / r.F : 0;
-                if (jl < u) u = jl;
-            }
-            if (u < upto) upto = u;
-        }
-        if (alike && first >= 0 && upto >= 1024 && upto < out_frames) j_uni = upto;
-    }
+    const uint64_t j_uni = fast_ok ? mp::alike_cut(srcs_host, n_sources, 1, to_rate, out_frames) : 0;
     hipStream_t st = rh::as_stream(stream);
     for (uint64_t j0 = 0; j0 < out_frames;) {
         const uint64_t seg_end = j0 < j_uni ? j_uni : out_frames;
         const uint32_t nf = (uint32_t)(seg_end - j0 < step ? seg_end - j0 : step);
-        SpTable tbl;
-        uint32_t k = 0, nr = 0;
-        bool cont = false, mono = true;
-        auto clear_rates = [&]() {
-            for (uint32_t q = 0; q < kSpRates; ++q) tbl.r[q] = SpRate{0u, 1u, 0u, 1.0f};
-            nr = 0;
-            mono = true;
-        };
-        clear_rates();
-        auto launch = [&]() {
-            {  // the fast case (k_spatial_mix_mono2): mono sources of one rate, a stereo mix, no source that ends inside the launch
-                bool fast = fast_ok && k > 0 && nr == 1 && mono;
-                const uint64_t il_max = ((uint64_t)tbl.r[0].r0 + (uint64_t)(nf - 1) * tbl.r[0].F) / tbl.r[0].T;
-                const bool lerp = tbl.r[0].F != tbl.r[0].T;
+        mp::walk_rates<mp::RateLaunch>(
+            n_sources, true,  // (no source reaches these frames: the mix is +0.0 there)
+            [&](uint32_t s, uint32_t *F, uint32_t *T, uint32_t *r0, uint64_t *i0) {
+                if (srcs_host[s].frames <= j0) return false;
+                mp::reduce(srcs_host[s].from_rate, to_rate, F, T);
+                mp::tap_of(srcs_host[s].phase, j0, *F, *T, i0, r0);  // position of frame j0 between its taps, from the block's first tap on
+                return true;
+            },
+            [&](const mp::RateLaunch &L) {
+                SpTable tbl;
+                for (uint32_t q = 0; q < kSpRates; ++q) tbl.r[q] = L.r[q];
+                uint32_t k = 0;
+                bool mono = true;
+                for (; k < L.n; ++k) {
+                    const uint32_t s = L.src[k];
+                    const rh_wide_src &x = srcs_host[s];
+                    const Red red = red_of(s, L.r[L.rate[k]]);
+                    const uint64_t i0 = L.i0[k];  // (what key worked out: no second gcd, no second division)
+                    const uint32_t r0 = L.r[L.rate[k]].r0;
+                    SpDesc &d = tbl.d[k];
+                    d.data = x.data + i0 * x.channels;
+                    d.ch = x.channels;
+                    d.frames = (uint32_t)(x.frames - j0 < nf ? x.frames - j0 : nf);
+                    d.last = x.last == 0xffffffffu ? 0xffffffffu : (x.last >= i0 ? (uint32_t)(x.last - i0) : 0u);
+                    d.rate = L.rate[k];
+                    d.Tf = red.F == red.T ? 0.0f : (float)red.T;
+                    d.pad = 0;
+                    // the step tables from the launch's first source frame on: sample K0 = i0 * channels of the emitter's output
+                    const uint64_t K0 = i0 * channels;
+                    const uint64_t reach = (((uint64_t)r0 + (uint64_t)(d.frames - 1) * red.F) / red.T + 2) * channels;  // (<= 2^30: `step`)
+                    const uint64_t gp = gain_steps_host[3 * (size_t)s + 1];
+                    d.gains = gains_dev_host[s] + ((red.g0 + K0) / gp) * channels;
+                    d.g = step_div(red.g0 + K0, gp, reach);
+                    d.factors = nullptr;
+                    d.f = mp::kStepNone;
+                    if (const float *f = factors_of(s)) {
+                        const uint64_t fp = factor_steps_host[3 * (size_t)s + 1];
+                        d.factors = f + (red.f0 + K0) / fp;
+                        d.f = step_div(red.f0 + K0, fp, reach);
+                    }
+                    mono = mono && x.channels == 1;
+                }
+                // the fast case (k_spatial_mix_mono2): mono sources of one rate, a stereo mix, no source that ends inside the launch
+                bool fast = fast_ok && k > 0 && L.nr == 1 && mono;
+                const bool lerp = L.r[0].F != L.r[0].T;
+                const uint64_t il_max = mp::last_tap(L.r[0], nf);
                 for (uint32_t q = 0; q < k && fast; ++q) fast = tbl.d[q].frames == nf && (!lerp || il_max < tbl.d[q].last);
                 if (fast) {
                     SpFastTable u;
-                    u.F = tbl.r[0].F, u.T = tbl.r[0].T, u.r0 = tbl.r[0].r0, u.Tf = tbl.r[0].Tf;
+                    u.F = L.r[0].F, u.T = L.r[0].T, u.r0 = L.r[0].r0, u.Tf = L.r[0].Tf;
                     for (uint32_t q = 0; q < kSpChunk; ++q) {
                         const SpDesc &d = tbl.d[q < k ? q : 0];
                         u.d[q] = SpFastSrc{d.data, d.gains, d.factors, d.g, d.f};
                     }
                     const dim3 grid(rh::grid_for((size_t)nf, kSpFastFrames, 256u * 16u));
                     float2 *d = reinterpret_cast<float2 *>(dst + j0 * 2);
-                    if (cont && lerp) hipLaunchKernelGGL((k_spatial_mix_mono2<true, true>), grid, dim3(kBlock), 0, st, d, nf, u, k);
-                    else if (cont) hipLaunchKernelGGL((k_spatial_mix_mono2<true, false>), grid, dim3(kBlock), 0, st, d, nf, u, k);
+                    if (L.cont && lerp) hipLaunchKernelGGL((k_spatial_mix_mono2<true, true>), grid, dim3(kBlock), 0, st, d, nf, u, k);
+                    else if (L.cont) hipLaunchKernelGGL((k_spatial_mix_mono2<true, false>), grid, dim3(kBlock), 0, st, d, nf, u, k);
                     else if (lerp) hipLaunchKernelGGL((k_spatial_mix_mono2<false, true>), grid, dim3(kBlock), 0, st, d, nf, u, k);
                     else hipLaunchKernelGGL((k_spatial_mix_mono2<false, false>), grid, dim3(kBlock), 0, st, d, nf, u, k);
-                    cont = true;
-                    k = 0;
-                    clear_rates();
                     return;
                 }
-            }
-            while (k % kSpGroup) {  // whole groups: slots that reach no frame (and point at something readable: the first source's first tap and entries)
-                SpDesc &d = tbl.d[k++];
-                d = SpDesc{tbl.d[0].data, tbl.d[0].gains, nullptr, 1u, 0u, 0u, 0u, 0.0f, 0u, tbl.d[0].g, StepDiv{0u, 1u, 0u, 0u}};
-            }
-            const uint64_t total = (uint64_t)nf * channels;
-            const dim3 grid(rh::grid_for((size_t)total, kBlock, 256u * 16u));
-            float *d = dst + j0 * channels;
-            if (cont) hipLaunchKernelGGL(k_spatial_mix<true>, grid, dim3(kBlock), 0, st, d, channels, nf, tbl, k);
-            else hipLaunchKernelGGL(k_spatial_mix<false>, grid, dim3(kBlock), 0, st, d, channels, nf, tbl, k);
-            cont = true;
-            k = 0;
-            clear_rates();
-        };
-        for (uint32_t s = 0; s < n_sources; ++s) {
-            const rh_wide_src &x = srcs_host[s];
-            if (x.frames <= j0) continue;
-            const Red red = reduce(s);
-            const uint64_t p = (uint64_t)x.phase + j0 * red.F;  // position of frame j0 between its taps, from the block's first tap on
-            const uint64_t i0 = p / red.T;
-            const uint32_t r0 = (uint32_t)(p - i0 * red.T);
-            uint32_t q = 0;
-            while (q < nr && !(tbl.r[q].F == red.F && tbl.r[q].T == red.T && tbl.r[q].r0 == r0)) ++q;
-            if (q == nr && nr == kSpRates) {  // a fifth rate: what has been gathered goes first (the sum continues from the stored partial sum)
-                launch();
-                q = 0;
-            }
-            if (q == nr) tbl.r[nr++] = SpRate{red.F, red.T, r0, (float)red.T};
-            SpDesc &d = tbl.d[k++];
-            d.data = x.data + i0 * x.channels;
-            d.ch = x.channels;
-            d.frames = (uint32_t)(x.frames - j0 < nf ? x.frames - j0 : nf);
-            d.last = x.last == 0xffffffffu ? 0xffffffffu : (x.last >= i0 ? (uint32_t)(x.last - i0) : 0u);
-            d.rate = q;
-            d.Tf = red.F == red.T ? 0.0f : (float)red.T;
-            d.pad = 0;
-            // the step tables from the launch's first source frame on: sample K0 = i0 * channels of the emitter's output
-            const uint64_t K0 = i0 * channels;
-            const uint64_t reach = (((uint64_t)r0 + (uint64_t)(d.frames - 1) * red.F) / red.T + 2) * channels;  // (<= 2^30: `step`)
-            const uint64_t gp = gain_steps_host[3 * (size_t)s + 1];
-            d.gains = gains_dev_host[s] + ((red.g0 + K0) / gp) * channels;
-            d.g = step_div(red.g0 + K0, gp, reach);
-            d.factors = nullptr;
-            d.f = StepDiv{0u, 1u, 0u, 0u};
-            if (const float *f = factors_of(s)) {
-                const uint64_t fp = factor_steps_host[3 * (size_t)s + 1];
-                d.factors = f + (red.f0 + K0) / fp;
-                d.f = step_div(red.f0 + K0, fp, reach);
-            }
-            mono = mono && x.channels == 1;
-            if (k == kSpChunk) launch();
-        }
-        if (k || !cont) launch();  // (no source reaches these frames: the mix is +0.0 there)
+                // whole groups: slots that reach no frame (and point at something readable: the first source's first tap and entries)
+                while (k % kSpGroup) tbl.d[k++] = SpDesc{tbl.d[0].data, tbl.d[0].gains, nullptr, 1u, 0u, 0u, 0u, 0.0f, 0u, tbl.d[0].g, mp::kStepNone};
+                const uint64_t total = (uint64_t)nf * channels;
+                const dim3 grid(rh::grid_for((size_t)total, kBlock, 256u * 16u));
+                float *d = dst + j0 * channels;
+                if (L.cont) hipLaunchKernelGGL(k_spatial_mix<true>, grid, dim3(kBlock), 0, st, d, channels, nf, tbl, k);
+                else hipLaunchKernelGGL(k_spatial_mix<false>, grid, dim3(kBlock), 0, st, d, channels, nf, tbl, k);
+            });
         RH_CHECK_LAUNCH();
         j0 += nf;
     }

@@ -9,27 +9,22 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
-#include <numeric>
 #include <vector>
 
 #include "../../include/rodio_hip.h"
+#include "rh_mix_plan.h"
 
 namespace rh {
 namespace widebatch {
 
 constexpr uint32_t kBlock = 256;        // lanes of a workgroup: one output sample each, `per` times
-constexpr uint32_t kGroup = 4;          // sources whose tap loads leave together (k_wide_mix's kWideGroup); a mixer's slots are whole groups
+using mixplan::kGroup;                  // sources whose tap loads leave together; a mixer's slots are whole groups
 constexpr uint32_t kUniGroup = 8;       // ... of a mixer of alike sources (k_wide_mix_uniform's kUniGroup: sixteen loads a lane)
-constexpr uint32_t kRates = 4;         // (rate, phase) pairs of a mixer whose division a lane does once per sample (k_wide_mix's kWideRates)
+using mixplan::kRates;                  // (rate, phase) pairs of a mixer whose division a lane does once per sample
 constexpr uint32_t kOwnRate = kRates;   // Src::rate of a source beyond them: it divides for itself
 constexpr uint32_t kMaxTiles = 16384;   // above this many tiles a lane takes 2, 4, .. samples (256 CUs x 8 workgroups x 8 rounds)
 constexpr uint32_t kMaxPer = 4096;      // ... up to this many: a tile never exceeds 2^20 samples
-
-struct Rate {
-    uint32_t F, T;  // reduced rates (an unused slot: F = 0, T = 1)
-    uint32_t r0;    // the block's phase: (m0 F) mod T
-    float Tf;
-};
+using mixplan::Rate;
 struct Mixer {  // 104 bytes
     float *dst;
     uint32_t ch, frames;
@@ -60,17 +55,7 @@ struct Plan {
     std::vector<uint32_t> order;     // the mixers that have tiles, in launch order
 };
 
-// What rh_wide_mix_block's wide_check_src answers about one source: the reduced rates, and `fit` = the output frames a launch may cover
-// before the source's position r0 + j F leaves 32 bits.
-inline rh_status check_src(const rh_wide_src &x, uint32_t to_rate, uint64_t out_frames, uint32_t *F, uint32_t *T, uint64_t *fit) {
-    if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-    const uint32_t g = std::gcd(x.from_rate, to_rate);
-    *F = x.from_rate / g, *T = to_rate / g;
-    if ((uint64_t)*F * *T > 0xffffffffull) return RH_ERR_UNSUPPORTED;  // the reference multiplies in u32 (sample_rate.rs:157,173)
-    if (x.phase >= *T) return RH_ERR_INVALID;
-    *fit = (0xffffffffull - *T) / *F;
-    return RH_OK;
-}
+using mixplan::check_src;  // (a block that does not fit one launch is refused behind the mixer's table: rh_wide_mix_block cuts such a block)
 
 // Samples a lane takes (a tile is kBlock * per samples): 1, doubled while the batch would be more than kMaxTiles tiles.
 inline uint64_t count_tiles(const std::vector<Mixer> &mixers, uint64_t tile_samples) {

@@ -9,14 +9,15 @@
 // a mixer multiplies launches.  A workgroup serves one tile of one mixer: what it reads of the tables is the same in every lane and arrives
 // through scalar loads.  Bytes as rh_widemix.hip counts them: 4 C_s N_s per source in, 4 C M per mixer out.
 #include <cstring>
-#include <unordered_map>
 
 #include "rh_common.h"
+#include "rh_mix_dev.h"
 #include "rh_wide_batch_plan.h"
 
 namespace {
 
 namespace wb = rh::widebatch;
+namespace md = rh::mixdev;
 
 // A pointer that was loaded from a table is a generic one to the compiler (flat loads); the rows and the destinations are device memory.
 typedef const float __attribute__((address_space(1))) *global_in;
@@ -61,12 +62,7 @@ __device__ __forceinline__ void tile_uniform(global_out dst, const wb::Tile &til
             }
 #pragma unroll
             for (uint32_t u = 0; u < wb::kUniGroup; ++u) {
-                const float x = a[u] * g[u];
-                float v = x;
-                if (LERP) {
-                    const float y = b[u] * g[u];
-                    v = x + (y - x) * w / m.r[0].Tf;
-                }
+                const float v = md::amp_lerp(a[u], b[u], g[u], LERP, w, m.r[0].Tf);
                 acc += on[u] ? v : 0.0f;  // (+ 0.0 leaves a sum that started at + 0.0 as it is)
             }
         }
@@ -130,8 +126,8 @@ __global__ __launch_bounds__(wb::kBlock) void k_wide_batch(const wb::Tile *__res
                 }
                 Tf[u] = d.Tf;
                 g[u] = d.gain;
-                const uint32_t k = c < d.ch ? c : 0u;                         // channels.rs:59-70: k < from: the input channel; k == 1 of a mono source: its only one;
-                on[u] = j < d.frames && (c < d.ch || (c == 1u && d.ch == 1u));  // otherwise 0.0
+                const uint32_t k = md::in_channel(c, d.ch);
+                on[u] = j < d.frames && md::has_channel(c, d.ch);
                 lerp[u] = on[u] && d.Tf != 0.0f && i < d.last;
                 const global_in pa = (global_in)d.data + (on[u] ? (uint64_t)i * d.ch + k : 0ull);
                 a[u] = *pa;
@@ -139,12 +135,7 @@ __global__ __launch_bounds__(wb::kBlock) void k_wide_batch(const wb::Tile *__res
             }
 #pragma unroll
             for (uint32_t u = 0; u < wb::kGroup; ++u) {
-                const float x = a[u] * g[u];  // Amplify (amplify.rs:64) in front of the converter
-                float v = x;
-                if (lerp[u]) {
-                    const float y = b[u] * g[u];
-                    v = x + (y - x) * wv[u] / Tf[u];
-                }
+                const float v = md::amp_lerp(a[u], b[u], g[u], lerp[u], wv[u], Tf[u]);
                 acc += on[u] ? v : 0.0f;
             }
         }
@@ -152,48 +143,7 @@ __global__ __launch_bounds__(wb::kBlock) void k_wide_batch(const wb::Tile *__res
     }
 }
 
-// The tables' way to the device, as rh_crossfade's plan table goes (cf_upload, rh_mix2.hip): page-locked tables, a ring of them per stream,
-// each rewritten only after an event recorded behind the copy that read it has fired.  Used under the stream's scratch lock.  A table lives
-// as long as the process does.
-constexpr int kRing = 4;
-struct Stage {
-    char *h[kRing] = {};
-    size_t cap[kRing] = {};  // bytes
-    hipEvent_t read[kRing] = {};
-    int next = 0;
-};
-std::unordered_map<hipStream_t, Stage> g_stage;
 inline size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
-hipError_t upload(hipStream_t s, void *table_dev, const wb::Plan &p, size_t mixers_at, size_t srcs_at, size_t tiles_at, size_t bytes) {
-    Stage &st = g_stage[s];
-    const int k = st.next;
-    hipError_t e;
-    if (st.read[k]) {
-        if ((e = hipEventSynchronize(st.read[k])) != hipSuccess) return e;
-    } else if ((e = hipEventCreateWithFlags(&st.read[k], hipEventDisableTiming)) != hipSuccess) {
-        st.read[k] = nullptr;
-        return e;
-    }
-    if (st.cap[k] < bytes) {
-        if (st.h[k]) (void)hipHostFree(st.h[k]);
-        st.h[k] = nullptr, st.cap[k] = 0;
-        size_t cap = 1 << 16;
-        while (cap < bytes) cap *= 2;
-        if ((e = hipHostMalloc(reinterpret_cast<void **>(&st.h[k]), cap, hipHostMallocDefault)) != hipSuccess) {
-            st.h[k] = nullptr;
-            return e;
-        }
-        st.cap[k] = cap;
-    }
-    memcpy(st.h[k] + mixers_at, p.mixers.data(), p.mixers.size() * sizeof(wb::Mixer));
-    if (!p.srcs.empty()) memcpy(st.h[k] + srcs_at, p.srcs.data(), p.srcs.size() * sizeof(wb::Src));
-    memcpy(st.h[k] + tiles_at, p.tiles.data(), p.tiles.size() * sizeof(wb::Tile));
-    if ((e = hipMemcpyAsync(table_dev, st.h[k], bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    if ((e = hipEventRecord(st.read[k], s)) != hipSuccess) return e;
-    st.next = (k + 1) % kRing;
-    return hipSuccess;
-}
 
 }  // namespace
 
@@ -215,7 +165,12 @@ rh_status rh_wide_mix_batch(float *const *dsts_host, const uint32_t *channels_ho
     std::unique_lock<std::mutex> hold;
     void *scratch = nullptr;
     RH_HIP_TRY(rh::stream_scratch(s, bytes, &scratch, hold));
-    RH_HIP_TRY(upload(s, scratch, plan, mixers_at, srcs_at, tiles_at, bytes));
+    char *host = nullptr;  // the tables' way to the device: the stream's table ring (rh_common.h)
+    RH_HIP_TRY(rh::table_stage(s, bytes, &host));
+    memcpy(host + mixers_at, plan.mixers.data(), plan.mixers.size() * sizeof(wb::Mixer));
+    if (!plan.srcs.empty()) memcpy(host + srcs_at, plan.srcs.data(), plan.srcs.size() * sizeof(wb::Src));
+    memcpy(host + tiles_at, plan.tiles.data(), plan.tiles.size() * sizeof(wb::Tile));
+    RH_HIP_TRY(rh::table_send(s, scratch));
     const char *base = static_cast<const char *>(scratch);
     hipLaunchKernelGGL(k_wide_batch, dim3((uint32_t)plan.tiles.size()), dim3(wb::kBlock), 0, s, reinterpret_cast<const wb::Tile *>(base + tiles_at),
                        reinterpret_cast<const wb::Mixer *>(base + mixers_at), reinterpret_cast<const wb::Src *>(base + srcs_at));

@@ -15,23 +15,23 @@
 // is read once from memory (the second tap of a frame is the first tap of the next: L1 / L2), 4 S C_s N_s bytes in, 4 C M out.
 // The source table travels by value as a kernel argument (32 sources a launch; more continue from the stored partial sum).
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "rh_common.h"
+#include "rh_mix_dev.h"
+#include "rh_mix_plan.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr uint32_t kWideChunk = 32;  // sources a launch
-constexpr int kWideGroup = 4;        // ... walked in groups of this many, whose tap loads leave together
-constexpr uint32_t kWideRates = 4;   // ... of at most this many different (rate, phase) pairs: the position of an output frame between its taps is worked out once per pair
+namespace mp = rh::mixplan;
+namespace md = rh::mixdev;
 
-struct WideRate {
-    uint32_t F, T;  // reduced rates (an unused slot: F = 0, T = 1)
-    uint32_t r0;    // (m0 F) mod T
-    float Tf;
-};
+constexpr int kBlock = 256;
+constexpr uint32_t kWideChunk = mp::kChunk;  // sources a launch
+constexpr int kWideGroup = (int)mp::kGroup;  // ... walked in groups of this many, whose tap loads leave together
+constexpr uint32_t kWideRates = mp::kRates;  // ... of at most this many different (rate, phase) pairs: the position of an output frame between its taps is worked out once per pair
+using WideRate = mp::Rate;
+
 struct WideDesc {
     const float *data;  // the frame that holds the first tap of the launch's first output frame
     uint32_t ch;        // channels of the source
@@ -53,19 +53,7 @@ template <bool CONT>
 __global__ __launch_bounds__(kBlock) void k_wide_mix(float *__restrict__ dst, uint32_t to_ch, uint32_t out_frames, const WideTable tbl, uint32_t n_sources) {
     const uint64_t total = (uint64_t)out_frames * to_ch;
     const uint64_t stride = (uint64_t)gridDim.x * kBlock;
-    {
-        // The table lies in the kernel-argument segment and is read through the scalar cache, descriptor after descriptor: the first wave of
-        // a CU would miss on every line of it in turn (measured: 0.39 us per source, 12.5 us for a table of 32 -- whatever the block's length).
-        // One word of every line is asked for HERE, all requests in flight at once: one round trip, and the walk below hits.
-        const uint32_t *w = reinterpret_cast<const uint32_t *>(&tbl);
-        constexpr uint32_t kLines = (sizeof(WideTable) + 63) / 64;
-        uint32_t t[kLines], touch = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) t[q] = w[q * 16u];
-#pragma unroll
-        for (uint32_t q = 0; q < kLines; ++q) touch |= t[q];
-        asm volatile("" ::"s"(touch));
-    }
+    md::touch_table(tbl);  // (the first wave of a CU would miss on the table's lines one after the other)
     for (uint64_t o = (uint64_t)blockIdx.x * kBlock + threadIdx.x; o < total; o += stride) {
         const uint32_t j = (uint32_t)(o / to_ch);
         const uint32_t c = (uint32_t)(o - (uint64_t)j * to_ch);
@@ -91,8 +79,8 @@ __global__ __launch_bounds__(kBlock) void k_wide_mix(float *__restrict__ dst, ui
                 wv[u] = q == 0 ? w[0] : (q == 1 ? w[1] : (q == 2 ? w[2] : w[3]));
                 Tf[u] = d.Tf;
                 g[u] = d.gain;
-                const uint32_t k = c < d.ch ? c : 0u;                         // channels.rs:59-70: k < from: the input channel; k == 1 of a mono source: its only one;
-                on[u] = j < d.frames && (c < d.ch || (c == 1u && d.ch == 1u));  // otherwise 0.0
+                const uint32_t k = md::in_channel(c, d.ch);
+                on[u] = j < d.frames && md::has_channel(c, d.ch);
                 lerp[u] = on[u] && d.Tf != 0.0f && i < d.last;
                 const float *pa = d.data + (on[u] ? (uint64_t)i * d.ch + k : 0ull);
                 a[u] = *pa;
@@ -100,12 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_mix(float *__restrict__ dst, ui
             }
 #pragma unroll
             for (int u = 0; u < kWideGroup; ++u) {
-                const float x = a[u] * g[u];  // Amplify (amplify.rs:64) in front of the converter
-                float v = x;
-                if (lerp[u]) {
-                    const float y = b[u] * g[u];
-                    v = x + (y - x) * wv[u] / Tf[u];
-                }
+                const float v = md::amp_lerp(a[u], b[u], g[u], lerp[u], wv[u], Tf[u]);
                 acc += on[u] ? v : 0.0f;
             }
         }
@@ -155,12 +138,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_mix_uniform(float *__restrict__
             }
 #pragma unroll
             for (int u = 0; u < kUniGroup; ++u) {
-                const float x = a[u] * g[u];
-                float v = x;
-                if (LERP) {
-                    const float y = b[u] * g[u];
-                    v = x + (y - x) * w / tbl.Tf;
-                }
+                const float v = md::amp_lerp(a[u], b[u], g[u], LERP, w, tbl.Tf);
                 acc += s0 + u < nv ? v : 0.0f;  // (+ 0.0 leaves a sum that started at + 0.0 as it is)
             }
         }
@@ -217,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_rows(uint32_t to_ch, uint32_t o
         const uint32_t j = (uint32_t)(o / to_ch);
         const uint32_t c = (uint32_t)(o - (uint64_t)j * to_ch);
         uint32_t il[kWideRates];
-        float w[kWideRates];
+        float w[kWideRates];  // num as a float (math.rs:25 multiplies by it, then divides by T)
 #pragma unroll
         for (uint32_t q = 0; q < kWideRates; ++q) {
             const uint32_t p = tbl.r[q].r0 + j * tbl.r[q].F;  // (host: fits 32 bits)
@@ -236,9 +214,9 @@ __global__ __launch_bounds__(kBlock) void k_wide_rows(uint32_t to_ch, uint32_t o
             Tf[u] = d.Tf;
             g[u] = d.gain;
             row[u] = d.row;
-            const uint32_t k = c < d.ch ? c : 0u;  // channels.rs:59-70, as in k_wide_mix
+            const uint32_t k = md::in_channel(c, d.ch);
             reach[u] = j < d.frames;
-            on[u] = reach[u] && (c < d.ch || (c == 1u && d.ch == 1u));
+            on[u] = reach[u] && md::has_channel(c, d.ch);
             lerp[u] = on[u] && d.Tf != 0.0f && i < d.last;
             const float *pa = d.data + (on[u] ? (uint64_t)i * d.ch + k : 0ull);
             a[u] = *pa;
@@ -246,12 +224,7 @@ __global__ __launch_bounds__(kBlock) void k_wide_rows(uint32_t to_ch, uint32_t o
         }
 #pragma unroll
         for (int u = 0; u < kWideGroup; ++u) {
-            const float x = a[u] * g[u];  // Amplify (amplify.rs:64) in front of the converter
-            float v = x;
-            if (lerp[u]) {
-                const float y = b[u] * g[u];
-                v = x + (y - x) * wv[u] / Tf[u];
-            }
+            const float v = md::amp_lerp(a[u], b[u], g[u], lerp[u], wv[u], Tf[u]);
             if (reach[u]) row[u][o] = on[u] ? v : 0.0f;
         }
     }
@@ -268,17 +241,6 @@ __global__ __launch_bounds__(64) void k_wide_state_out(uint32_t to_ch, const Wid
     for (uint32_t t = threadIdx.x; t < 4u * to_ch; t += 64) to[t] = from[t];
 }
 
-// What rh_wide_mix_block checks of a table before its first launch: the same answers, for an entry that launches in front of it.
-// fit: the output frames a launch may cover before a source's position r0 + j F leaves 32 bits.
-rh_status wide_check_src(const rh_wide_src &x, uint32_t to_rate, uint64_t out_frames, uint32_t *F, uint32_t *T, uint64_t *fit) {
-    if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-    const uint32_t g = std::gcd(x.from_rate, to_rate);
-    *F = x.from_rate / g, *T = to_rate / g;
-    if ((uint64_t)*F * *T > 0xffffffffull) return RH_ERR_UNSUPPORTED;
-    if (x.phase >= *T) return RH_ERR_INVALID;
-    *fit = (0xffffffffull - *T) / *F;
-    return *fit ? RH_OK : RH_ERR_UNSUPPORTED;
-}
 inline uint64_t wide_row_pitch(uint32_t channels, uint64_t out_frames) { return (out_frames * channels + 3) & ~3ull; }
 inline uint64_t wide_filtered_bytes(uint32_t channels, uint64_t out_frames, uint64_t n) { return n * (2 * wide_row_pitch(channels, out_frames) + 4ull * channels) * sizeof(float); }
 
@@ -295,112 +257,64 @@ rh_status rh_wide_mix_block(float *dst, uint32_t channels, uint32_t to_rate, uin
     std::vector<Red> red(n_sources);
     uint64_t step = out_frames;  // output frames per launch: r0 + j F must fit 32 bits for every source
     for (uint32_t s = 0; s < n_sources; ++s) {
-        const rh_wide_src &x = srcs_host[s];
-        if (x.frames == 0) continue;
-        if (!x.data || x.channels == 0 || x.from_rate == 0 || x.frames > out_frames) return RH_ERR_INVALID;
-        const uint32_t g = std::gcd(x.from_rate, to_rate);
-        red[s] = Red{x.from_rate / g, to_rate / g};
-        if ((uint64_t)red[s].F * red[s].T > 0xffffffffull) return RH_ERR_UNSUPPORTED;  // the reference multiplies in u32 (sample_rate.rs:157,173)
-        if (x.phase >= red[s].T) return RH_ERR_INVALID;
-        const uint64_t fit = (0xffffffffull - red[s].T) / red[s].F;
+        if (srcs_host[s].frames == 0) continue;
+        uint64_t fit;
+        const rh_status st = mp::check_src(srcs_host[s], to_rate, out_frames, &red[s].F, &red[s].T, &fit);
+        if (st != RH_OK) return st;
         if (fit < step) step = fit;
     }
     if (step == 0) return RH_ERR_UNSUPPORTED;
     // Alike sources (one rate and phase, the mixer's layout): the frames in front of the first one that ends -- or whose last frame a tap reaches --
     // go to the uniform kernel as a launch of their own, the rest to the general one.
-    uint64_t j_uni = 0;
-    {
-        bool alike = true;
-        int first = -1;
-        uint64_t upto = out_frames;
-        for (uint32_t s = 0; s < n_sources && alike; ++s) {
-            const rh_wide_src &x = srcs_host[s];
-            if (x.frames == 0) continue;
-            if (first < 0) first = (int)s;
-            alike = x.channels == channels && red[s].F == red[(size_t)first].F && red[s].T == red[(size_t)first].T && x.phase == srcs_host[first].phase;
-            uint64_t u = x.frames;
-            if (x.last != 0xffffffffu && red[s].F != red[s].T) {  // il(j) >= last  <=>  phase + j F >= last T
-                const uint64_t need = (uint64_t)x.last * red[s].T;
-                const uint64_t jl = need > x.phase ? (need - x.phase + red[s].F - 1) / red[s].F : 0;
-                if (jl < u) u = jl;
-            }
-            if (u < upto) upto = u;
-        }
-        if (alike && first >= 0 && upto >= 1024 && upto < out_frames) j_uni = upto;
-    }
+    const uint64_t j_uni = mp::alike_cut(srcs_host, n_sources, channels, to_rate, out_frames);
+    hipStream_t st = rh::as_stream(stream);
     for (uint64_t j0 = 0; j0 < out_frames;) {
         const uint64_t seg_end = j0 < j_uni ? j_uni : out_frames;
         const uint32_t nf = (uint32_t)(seg_end - j0 < step ? seg_end - j0 : step);
-        WideTable tbl;
-        uint32_t k = 0, nr = 0;
-        bool cont = false;
-        auto clear_rates = [&]() {
-            for (uint32_t q = 0; q < kWideRates; ++q) tbl.r[q] = WideRate{0u, 1u, 0u, 1.0f};
-            nr = 0;
-        };
-        clear_rates();
-        auto launch = [&]() {
-            {  // the uniform case (k_wide_mix_uniform): one rate, the mixer's layout, no source that ends inside the launch
-                bool uni = k > 0 && nr == 1;
-                const uint64_t il_max = ((uint64_t)tbl.r[0].r0 + (uint64_t)(nf - 1) * tbl.r[0].F) / tbl.r[0].T;
-                const bool lerp = tbl.r[0].F != tbl.r[0].T;
+        float *const d0 = dst + j0 * channels;
+        const uint64_t total = (uint64_t)nf * channels;
+        mp::walk_rates<mp::RateLaunch>(
+            n_sources, true,  // (no source reaches these frames: the mix is +0.0 there)
+            [&](uint32_t s, uint32_t *F, uint32_t *T, uint32_t *r0, uint64_t *i0) {
+                if (srcs_host[s].frames <= j0) return false;
+                *F = red[s].F, *T = red[s].T;
+                mp::tap_of(srcs_host[s].phase, j0, *F, *T, i0, r0);  // position of frame j0 between its taps, from the block's first tap on
+                return true;
+            },
+            [&](const mp::RateLaunch &L) {
+                WideTable tbl;
+                for (uint32_t q = 0; q < kWideRates; ++q) tbl.r[q] = L.r[q];
+                uint32_t k = 0;
+                for (; k < L.n; ++k) {
+                    const uint32_t s = L.src[k];
+                    const rh_wide_src &x = srcs_host[s];
+                    const uint64_t i0 = L.i0[k];
+                    tbl.d[k] = WideDesc{x.data + i0 * x.channels, x.channels, (uint32_t)(x.frames - j0 < nf ? x.frames - j0 : nf),
+                                        x.last == 0xffffffffu ? 0xffffffffu : (x.last >= i0 ? (uint32_t)(x.last - i0) : 0u), L.rate[k], x.gain, red[s].F == red[s].T ? 0.0f : (float)red[s].T};
+                }
+                // the uniform case (k_wide_mix_uniform): one rate, the mixer's layout, no source that ends inside the launch
+                bool uni = k > 0 && L.nr == 1 && !rh::knob(rh::K_WIDE_GENERAL);
+                const bool lerp = L.r[0].F != L.r[0].T;
+                const uint64_t il_max = mp::last_tap(L.r[0], nf);
                 for (uint32_t q = 0; q < k && uni; ++q) uni = tbl.d[q].ch == channels && tbl.d[q].frames == nf && (!lerp || il_max < tbl.d[q].last);
-                if (uni && !rh::knob(rh::K_WIDE_GENERAL)) {
+                if (uni) {
                     WideUniTable u;
-                    u.F = tbl.r[0].F, u.T = tbl.r[0].T, u.r0 = tbl.r[0].r0, u.ch = channels, u.Tf = tbl.r[0].Tf;
+                    u.F = L.r[0].F, u.T = L.r[0].T, u.r0 = L.r[0].r0, u.ch = channels, u.Tf = L.r[0].Tf;
                     u.pad[0] = u.pad[1] = u.pad[2] = 0;
                     for (uint32_t q = 0; q < kWideChunk; ++q) u.d[q] = WideUniSrc{tbl.d[q < k ? q : 0].data, q < k ? tbl.d[q].gain : 0.0f, 0u};
-                    const uint64_t total = (uint64_t)nf * channels;
                     const dim3 grid(rh::grid_for((size_t)total, kBlock, 256u * 16u));
-                    float *d = dst + j0 * channels;
-                    hipStream_t st = rh::as_stream(stream);
-                    if (cont && lerp) hipLaunchKernelGGL((k_wide_mix_uniform<true, true>), grid, dim3(kBlock), 0, st, d, nf, u, k);
-                    else if (cont) hipLaunchKernelGGL((k_wide_mix_uniform<true, false>), grid, dim3(kBlock), 0, st, d, nf, u, k);
-                    else if (lerp) hipLaunchKernelGGL((k_wide_mix_uniform<false, true>), grid, dim3(kBlock), 0, st, d, nf, u, k);
-                    else hipLaunchKernelGGL((k_wide_mix_uniform<false, false>), grid, dim3(kBlock), 0, st, d, nf, u, k);
-                    cont = true;
-                    k = 0;
-                    clear_rates();
+                    if (L.cont && lerp) hipLaunchKernelGGL((k_wide_mix_uniform<true, true>), grid, dim3(kBlock), 0, st, d0, nf, u, k);
+                    else if (L.cont) hipLaunchKernelGGL((k_wide_mix_uniform<true, false>), grid, dim3(kBlock), 0, st, d0, nf, u, k);
+                    else if (lerp) hipLaunchKernelGGL((k_wide_mix_uniform<false, true>), grid, dim3(kBlock), 0, st, d0, nf, u, k);
+                    else hipLaunchKernelGGL((k_wide_mix_uniform<false, false>), grid, dim3(kBlock), 0, st, d0, nf, u, k);
                     return;
                 }
-            }
-            while (k % kWideGroup) {  // whole groups: slots that reach no frame (and point at something readable: the first source's first tap)
-                WideDesc &d = tbl.d[k++];
-                d = WideDesc{tbl.d[0].data, 1u, 0u, 0u, 0u, 0.0f, 0.0f};
-            }
-            const uint64_t total = (uint64_t)nf * channels;
-            const dim3 grid(rh::grid_for((size_t)total, kBlock, 256u * 16u));
-            float *d = dst + j0 * channels;
-            if (cont) hipLaunchKernelGGL(k_wide_mix<true>, grid, dim3(kBlock), 0, rh::as_stream(stream), d, channels, nf, tbl, k);
-            else hipLaunchKernelGGL(k_wide_mix<false>, grid, dim3(kBlock), 0, rh::as_stream(stream), d, channels, nf, tbl, k);
-            cont = true;
-            k = 0;
-            clear_rates();
-        };
-        for (uint32_t s = 0; s < n_sources; ++s) {
-            const rh_wide_src &x = srcs_host[s];
-            if (x.frames <= j0) continue;
-            const uint64_t p = (uint64_t)x.phase + j0 * red[s].F;  // position of frame j0 between its taps, from the block's first tap on
-            const uint64_t i0 = p / red[s].T;
-            const uint32_t r0 = (uint32_t)(p - i0 * red[s].T);
-            uint32_t q = 0;
-            while (q < nr && !(tbl.r[q].F == red[s].F && tbl.r[q].T == red[s].T && tbl.r[q].r0 == r0)) ++q;
-            if (q == nr && nr == kWideRates) {  // a fifth rate: what has been gathered goes first (the sum continues from the stored partial sum)
-                launch();
-                q = 0;
-            }
-            if (q == nr) tbl.r[nr++] = WideRate{red[s].F, red[s].T, r0, (float)red[s].T};
-            WideDesc &d = tbl.d[k++];
-            d.data = x.data + i0 * x.channels;
-            d.ch = x.channels;
-            d.frames = (uint32_t)(x.frames - j0 < nf ? x.frames - j0 : nf);
-            d.last = x.last == 0xffffffffu ? 0xffffffffu : (x.last >= i0 ? (uint32_t)(x.last - i0) : 0u);
-            d.rate = q;
-            d.gain = x.gain;
-            d.Tf = red[s].F == red[s].T ? 0.0f : (float)red[s].T;
-            if (k == kWideChunk) launch();
-        }
-        if (k || !cont) launch();  // (no source reaches these frames: the mix is +0.0 there)
+                // whole groups: slots that reach no frame (and point at something readable: the first source's first tap)
+                while (k % kWideGroup) tbl.d[k++] = WideDesc{tbl.d[0].data, 1u, 0u, 0u, 0u, 0.0f, 0.0f};
+                const dim3 grid(rh::grid_for((size_t)total, kBlock, 256u * 16u));
+                if (L.cont) hipLaunchKernelGGL(k_wide_mix<true>, grid, dim3(kBlock), 0, st, d0, channels, nf, tbl, k);
+                else hipLaunchKernelGGL(k_wide_mix<false>, grid, dim3(kBlock), 0, st, d0, channels, nf, tbl, k);
+            });
         RH_CHECK_LAUNCH();
         j0 += nf;
     }
@@ -437,8 +351,9 @@ rh_status rh_wide_mix_block_filtered(float *dst, uint32_t channels, uint32_t to_
         if (x.frames == 0) continue;
         uint32_t F, T;
         uint64_t fit;
-        const rh_status st = wide_check_src(x, to_rate, out_frames, &F, &T, &fit);
+        const rh_status st = mp::check_src(x, to_rate, out_frames, &F, &T, &fit);
         if (st != RH_OK) return st;
+        if (fit == 0) return RH_ERR_UNSUPPORTED;
         if (kinds_host[s] < 0) continue;
         if (fit < x.frames) return RH_ERR_UNSUPPORTED;
         rows.push_back(Row{s, F, T, x.frames == out_frames});
@@ -469,46 +384,27 @@ rh_status rh_wide_mix_block_filtered(float *dst, uint32_t channels, uint32_t to_
     float *const conv = static_cast<float *>(scratch), *const filt = conv + R * pitch, *const states = filt + R * pitch;
     hipStream_t hs = rh::as_stream(stream);
     // 1. the converter: a launch per 32 rows (or per four different (rate, phase) pairs)
-    {
-        WideRowTable tbl;
-        uint32_t k = 0, nr = 0;
-        auto clear_rates = [&]() {
-            for (uint32_t q = 0; q < kWideRates; ++q) tbl.r[q] = WideRate{0u, 1u, 0u, 1.0f};
-            nr = 0;
-        };
-        clear_rates();
-        auto launch = [&]() {
+    mp::walk_rates<mp::RateLaunch>(
+        (uint32_t)R, false,
+        [&](uint32_t i, uint32_t *F, uint32_t *T, uint32_t *r0, uint64_t *) {
+            *F = rows[i].F, *T = rows[i].T, *r0 = srcs_host[rows[i].s].phase;
+            return true;
+        },
+        [&](const mp::RateLaunch &L) {
+            WideRowTable tbl;
+            for (uint32_t q = 0; q < kWideRates; ++q) tbl.r[q] = L.r[q];
+            uint32_t k = 0;
+            for (; k < L.n; ++k) {
+                const size_t i = L.src[k];
+                const rh_wide_src &x = srcs_host[rows[i].s];
+                tbl.d[k] = WideRowDesc{x.data, conv + i * pitch, states_host ? states_host[rows[i].s] : nullptr, carried ? states + i * 4 * (size_t)channels : nullptr,
+                                       x.channels, (uint32_t)x.frames, x.last, L.rate[k], x.gain, rows[i].F == rows[i].T ? 0.0f : (float)rows[i].T};
+            }
             while (k % kWideGroup) tbl.d[k++] = WideRowDesc{tbl.d[0].data, nullptr, nullptr, nullptr, 1u, 0u, 0u, 0u, 0.0f, 0.0f};  // (whole groups: slots that reach no frame)
             const uint64_t total = out_frames * channels;
             hipLaunchKernelGGL(k_wide_rows, dim3(rh::grid_for((size_t)total, kBlock, 256u * 16u), k / kWideGroup), dim3(kBlock), 0, hs, channels, (uint32_t)out_frames, tbl);
-            k = 0;
-            clear_rates();
-        };
-        for (size_t i = 0; i < R; ++i) {
-            const rh_wide_src &x = srcs_host[rows[i].s];
-            uint32_t q = 0;
-            while (q < nr && !(tbl.r[q].F == rows[i].F && tbl.r[q].T == rows[i].T && tbl.r[q].r0 == x.phase)) ++q;
-            if (q == nr && nr == kWideRates) {
-                launch();
-                q = 0;
-            }
-            if (q == nr) tbl.r[nr++] = WideRate{rows[i].F, rows[i].T, x.phase, (float)rows[i].T};
-            WideRowDesc &d = tbl.d[k++];
-            d.data = x.data;
-            d.row = conv + i * pitch;
-            d.state = states_host ? states_host[rows[i].s] : nullptr;
-            d.state_row = carried ? states + i * 4 * (size_t)channels : nullptr;
-            d.ch = x.channels;
-            d.frames = (uint32_t)x.frames;
-            d.last = x.last;
-            d.rate = q;
-            d.gain = x.gain;
-            d.Tf = rows[i].F == rows[i].T ? 0.0f : (float)rows[i].T;
-            if (k == kWideChunk) launch();
-        }
-        if (k) launch();
-        RH_CHECK_LAUNCH();
-    }
+        });
+    RH_CHECK_LAUNCH();
     // 2. the filter: a batch per coefficient set where the rows lie back to back on 16-byte boundaries, and the rows that end inside the
     //    block one by one.  Mode 1 only for what the contract covers; rh_biquad itself continues in mode 0 where its scan kernel declines.
     for (size_t i = 0; i < R;) {

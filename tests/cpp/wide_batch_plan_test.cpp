@@ -1,7 +1,7 @@
 // wide_batch_plan_test.cpp -- the plan of rh_wide_mix_batch (rodio_amd/csrc/rh_wide_batch_plan.h) without a GPU: every output sample of every
 // mixer lies in exactly one tile and no tile crosses a mixer, the source ranges are the prefix sums of the counts, the slots are the sources
 // that reach the block in insertion order with the rate each one reads, every refusal of the header is answered, and the 32-bit fit is
-// wide_check_src's formula written out a second time.  TEST INFRASTRUCTURE: plain g++, no HIP, no library.  Pointers are never followed.
+// check_src's formula (rh_mix_plan.h) written out a second time.  TEST INFRASTRUCTURE: plain g++, no HIP, no library.  Pointers are never followed.
 //
 //     wide_batch_plan_test [seed [random batches]]
 #include <algorithm>
@@ -256,7 +256,7 @@ static int test_refusals() {
     return n;
 }
 
-// The fit against wide_check_src's formula, (2^32 - 1 - T) / F, on both sides of the boundary, and its meaning: the last position fits.
+// The fit against check_src's formula (rh_mix_plan.h), (2^32 - 1 - T) / F, on both sides of the boundary, and its meaning: the last position fits.
 static long test_fit() {
     long n = 0;
     const uint32_t pairs[][2] = {{65521, 48000}, {96000, 8000}, {48000, 44100}, {4294967291u, 1}, {65535, 65537}, {192000, 1}, {3, 2}};

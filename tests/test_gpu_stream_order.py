@@ -1292,7 +1292,7 @@ def test_nine_stream_blocks_behind_one_gate_and_the_fifth_waits_for_a_ring_slot(
 
 
 def test_nine_crossfades_behind_one_gate_and_the_fifth_waits_for_a_ring_slot(G, O, side, delay):
-    """Eight fused batches and a composed one.  cf_upload's pinned ring has four slots: calls 1-4 return while the gate is pending, call 5
+    """Eight fused batches and a composed one.  The stream's pinned table ring (rh::table_stage) has four slots: calls 1-4 return while the gate is pending, call 5
     waits for the copy that call 1 queued (behind the gate), so it and what follows return after it.  Every destination is its own."""
 
     def build(k):

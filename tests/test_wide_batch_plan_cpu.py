@@ -1,7 +1,7 @@
 """The plan of rh_wide_mix_batch (rodio_amd/csrc/rh_wide_batch_plan.h), no GPU: tests/cpp/wide_batch_plan_test plans random batches and the
 shapes of the GPU tests and of the benchmark and checks that every output sample of every mixer lies in exactly one tile, that no tile
 crosses a mixer, that the source ranges are the prefix sums of the counts, that every refusal of the header is answered and that the
-32-bit fit is wide_check_src's formula.  The same stand-alone program runs a second time built with -fsanitize=address,undefined."""
+32-bit fit is check_src's formula (rh_mix_plan.h).  The same stand-alone program runs a second time built with -fsanitize=address,undefined."""
 import importlib.util
 import os
 import shutil
